@@ -47,6 +47,11 @@ HTTP I/O, decode, batcher + JSON, load generator, ...; ``stage_cpu_us_per_req``:
 JSON from thread CPU clocks), ``mean_batch``, ``shared_front`` (N > 1: every rank on one SO_REUSEPORT port
 driven by one node-level load generator; ``--front shared`` makes that the headline).
 
+A plain run measures the headline only: set-up, warm-up, the timed window, the result line.  ``--full`` adds
+the measurements that take runs of their own after the window: ``levels``, ``inproc``, ``bf16``,
+``shared_front``, ``engine_req_s`` / ``engine_rgb_req_s`` (without it those keys are empty or absent).
+``--dump-outputs DIR`` writes what the window's clients received as ``DIR/<name>.npy`` (dump_outputs).
+
 ``--fake-engine`` replaces the GPU pipeline by the host-only EchoInstance (CPU tests of the whole
 harness, including the N-rank path over gloo: ARENA_DIST_BACKEND=gloo).
 """
@@ -154,9 +159,10 @@ def engine_throughput(ex, images, B: int, batches: int, jpeg_set=None) -> float:
     return (len(done_t) - depth) * B / (done_t[-1] - done_t[depth - 1])
 
 
-def _window(a, info, D, sync, completed, wait_until, users: int, on_open=None):
+def _window(a, info, D, sync, completed, wait_until, users: int, on_open=None, on_start=None):
     """Warm-up (>= --warmup steps, >= 4 requests per user, >= --min-warmup-s), barrier + sync, then the window
-    of exactly --steps steps; returns (seconds, first completion index of the window)."""
+    of exactly --steps steps; returns (seconds, first completion index of the window).  ``on_start`` is given
+    the index one past the window's last completion as soon as the window is open."""
     R = a.batch * a.step_batches
     tw = time.perf_counter()
     wait_until(max(a.warmup * R, 4 * users))
@@ -170,6 +176,8 @@ def _window(a, info, D, sync, completed, wait_until, users: int, on_open=None):
             on_open()
         c0 = completed()
         t0 = time.perf_counter()
+        if on_start is not None:
+            on_start(c0 + a.steps * R)
         wait_until(c0 + a.steps * R)
         sync()
         t1 = time.perf_counter()
@@ -249,25 +257,30 @@ def _batch_mean(b0: dict, b1: dict) -> float | None:
     return round((b1["requests"] - b0["requests"]) / nb, 2) if nb > 0 else None
 
 
-def measure_http(port: int, reqs: list[bytes], a, info, D, sync, users: int, threads: int, fe=None, batcher=None):
-    """Closed-loop HTTP window on one rank: (seconds, latencies s, detections, statuses, extras)."""
+def measure_http(port: int, reqs: list[bytes], a, info, D, sync, users: int, threads: int, fe=None, batcher=None,
+                 capture: dict | None = None):
+    """Closed-loop HTTP window on one rank: (seconds, latencies s, detections, statuses, extras).  ``capture``
+    (a dict) receives the window's latest response body per request under ``bodies`` and the window's first
+    completion index under ``c0`` (--dump-outputs)."""
     from inference_arena_amd.ops import native
 
     lg = native().HttpLoadGen({"host": "127.0.0.1", "port": port, "users": users,
-                               "threads": max(1, min(threads, users))}, reqs)
-    return _measure(lg, a, info, D, sync, users, fe, batcher)
+                               "threads": max(1, min(threads, users)), "keep_bodies": capture is not None}, reqs)
+    return _measure(lg, a, info, D, sync, users, fe, batcher, capture)
 
 
-def measure_inproc(fe, uploads: list[bytes], a, info, D, sync, users: int, batcher=None):
+def measure_inproc(fe, uploads: list[bytes], a, info, D, sync, users: int, batcher=None, capture: dict | None = None):
     """The same window without the HTTP layer: a C++ closed loop submits the uploads to the front end's decode
     stage in process (HttpFrontEnd::submit_local); decode, batching, device, JSON unchanged."""
     from inference_arena_amd.ops import native
 
     lg = native().LocalLoadGen(fe, uploads, users)
-    return _measure(lg, a, info, D, sync, users, fe, batcher)
+    if capture is not None:
+        lg.keep_bodies()
+    return _measure(lg, a, info, D, sync, users, fe, batcher, capture)
 
 
-def _measure(lg, a, info, D, sync, users, fe, batcher):
+def _measure(lg, a, info, D, sync, users, fe, batcher, capture=None):
     lg.start()
 
     def wait_until(n):
@@ -291,7 +304,8 @@ def _measure(lg, a, info, D, sync, users, fe, batcher):
                     holder["busy"] = BusySampler(ident.get("pci_bus_id"), torch_device()).start()
                 except Exception as e:  # noqa: BLE001 - a missing sampler must not fail the measurement
                     log(f"gpu busy sampler unavailable: {e}")
-        window, c0 = _window(a, info, D, sync, lg.completed, wait_until, users, on_open=opened)
+        window, c0 = _window(a, info, D, sync, lg.completed, wait_until, users, on_open=opened,
+                             on_start=lg.capture_until if capture is not None else None)
         busy = holder["busy"].stop() if "busy" in holder else None
         n = a.steps * a.batch * a.step_batches
         us, stages = holder["cpu"].per_request(n)
@@ -302,6 +316,8 @@ def _measure(lg, a, info, D, sync, users, fe, batcher):
             cpu["mean_batch"] = _batch_mean(holder["b0"], batcher.stats())
     finally:
         lg.stop(60.0)
+    if capture is not None:
+        capture.update(lg.bodies(), c0=c0)
     r = lg.records(c0, c0 + a.steps * a.batch * a.step_batches)
     return (window, r["latency"].astype(np.float64), r["dets"].astype(np.int64), r["status"].astype(np.int64), cpu)
 
@@ -358,6 +374,53 @@ def make_front(batcher, pool, plan: dict, a, port: int = 0, reuse_port: bool = T
                                   "max_image_pixels": max_image_pixels(), "reuse_port": reuse_port})
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory: str, capture: dict) -> dict:
+    """--dump-outputs: what the clients of the headline window received (rank 0's load generator), as float32
+    arrays in ``directory``.
+
+    Row i of every array is upload i of the workload (the same seeded images in the same order on every run);
+    its values are the detections of the last /predict response that upload got inside the timed window, in
+    the response's order, zero-padded to the largest detection count.  With a step of at least
+    uploads + users requests (the default is 1024 against 100 + 256) that response belongs to the last step.
+
+    ``answered`` 1 where the upload was answered in the window (0: the row is all zeros), ``num_detections``,
+    ``boxes`` [x1, y1, x2, y2], ``det_confidence``, ``det_class_id``, ``cls_class_id`` and ``cls_confidence``
+    (top-1 classification of each crop).  Request ids and timings are left out: they differ from run to run."""
+    rows = []
+    for body, at in zip(capture["body"], capture["at"]):
+        # (an error response carries no detections: left unanswered, and counted under ``errors``)
+        dets = json.loads(body).get("detections") if at >= capture["c0"] and body else None
+        rows.append(dets)
+    n, m = len(rows), max([len(d) for d in rows if d] + [1])
+    out = {"answered": np.zeros(n, np.float32), "num_detections": np.zeros(n, np.float32),
+           "boxes": np.zeros((n, m, 4), np.float32), "det_confidence": np.zeros((n, m), np.float32),
+           "det_class_id": np.zeros((n, m), np.float32), "cls_class_id": np.zeros((n, m), np.float32),
+           "cls_confidence": np.zeros((n, m), np.float32)}
+    for i, dets in enumerate(rows):
+        if dets is None:
+            continue
+        out["answered"][i] = 1
+        out["num_detections"][i] = len(dets)
+        for j, d in enumerate(dets):
+            det, cls = d["detection"], d["classification"]
+            out["boxes"][i, j] = [det["x1"], det["y1"], det["x2"], det["y2"]]
+            out["det_confidence"][i, j] = det["confidence"]
+            out["det_class_id"][i, j] = det["class_id"]
+            out["cls_class_id"][i, j] = cls["class_id"]
+            out["cls_confidence"][i, j] = cls["confidence"]
+    total = sum(v.nbytes for v in out.values())
+    assert total <= DUMP_MAX_BYTES, total  # a few KB per upload
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, v in out.items():
+        np.save(d / f"{name}.npy", v)
+    return {"dir": str(d), "arrays": sorted(out), "uploads": n, "answered": int(out["answered"].sum()),
+            "bytes": total}
+
+
 def summarize(window: float, lat, a, info, D) -> dict:
     w = D.allreduce_max(window, info)
     flat = np.asarray([x for lst in D.allgather_floats([float(x) for x in lat], info) for x in lst]) * 1e3
@@ -408,8 +471,19 @@ def main(argv=None) -> int:
                     help="N > 1: also measure one node-level front door (secondary key 'shared_front')")
     ap.add_argument("--crop-cap", type=int, default=None)
     ap.add_argument("--fake-engine", action="store_true", help="host-only EchoInstance instead of the GPU (CPU tests)")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the secondary measurements, each a run of its own after the headline window: "
+                         "--latency-levels, --secondary-inproc/-bf16/-shared-front and the engine-only rates "
+                         "(--engine-batches); without it only the headline is measured and those keys stay empty")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline window's requests were answered with (the last response per "
+                         "upload, parsed from the JSON) as DIR/<name>.npy, float32 (dump_outputs)")
     a = ap.parse_args(argv)
     raw_argv = list(sys.argv[1:] if argv is None else argv)
+    if not a.full:
+        a.latency_levels = ""
+        a.secondary_inproc = a.secondary_bf16 = a.secondary_shared_front = False
+        a.engine_batches = 0
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(raw_argv, a.gpus)
@@ -554,13 +628,16 @@ def main(argv=None) -> int:
         gc.freeze()
         headline_shared = a.front == "shared" and info.world > 1
         errs = 0
+        # --dump-outputs: rank 0's load generator keeps the headline window's response bodies
+        capture = {} if a.dump_outputs and info.is_main else None
         if not headline_shared:
             fe, batcher = serve(ex)
             if a.path == "http":
                 window, lat, crops, status, extras = measure_http(fe.port, reqs, a, info, D, sync, a.users,
-                                                                  plan["loadgen"], fe, batcher)
+                                                                  plan["loadgen"], fe, batcher, capture)
             else:
-                window, lat, crops, status, extras = measure_inproc(fe, jpegs_r, a, info, D, sync, a.users, batcher)
+                window, lat, crops, status, extras = measure_inproc(fe, jpegs_r, a, info, D, sync, a.users, batcher,
+                                                                    capture)
             close(fe, batcher)
             errs = int((status != 200).sum())
             lat = list(lat)
@@ -601,7 +678,7 @@ def main(argv=None) -> int:
                 a_node = argparse.Namespace(**vars(a))
                 a_node.step_batches = a.step_batches * info.world
                 res = measure_http(port, reqs, a_node, _Solo(), _SoloD(), sync, a.users * info.world,
-                                   plan["loadgen"] * 2, f3, b3)
+                                   plan["loadgen"] * 2, f3, b3, capture if headline_shared else None)
             D.barrier(info)
             close(f3, b3)
             if info.is_main:
@@ -728,6 +805,8 @@ def main(argv=None) -> int:
                 "shared_gpu_rehearsal": shared_gpu,
             }
             out.update(sec)
+            if capture is not None:
+                out["dumped_outputs"] = dump_outputs(a.dump_outputs, capture)
             print(json.dumps(out), flush=True)
     finally:
         for f, b in list(fronts):

@@ -967,6 +967,17 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("dst"), py::arg("src"), py::arg("what") = "peer copy", py::arg("can_access") = py::none(),
      "runtime/peer.h policy; can_access(dst, src) -> int overrides hipDeviceCanAccessPeer (tests)");
 
+  // BodyCapture -> {"body": [bytes per request], "at": int64 completion index of each (-1: none)}
+  auto bodies_py = [](const BodyCapture& c) {
+    py::list body;
+    for (const std::string& b : c.body) body.append(py::bytes(b));
+    py::array_t<int64_t> at((py::ssize_t)c.at.size());
+    for (size_t i = 0; i < c.at.size(); ++i) at.mutable_data()[i] = c.at[i];
+    py::dict d;
+    d["body"] = body;
+    d["at"] = at;
+    return d;
+  };
   py::class_<HttpLoadGen>(m, "HttpLoadGen")
       .def(py::init([](const py::dict& cfg, const py::list& requests) {
              LoadGenConfig c;
@@ -975,6 +986,7 @@ PYBIND11_MODULE(_C, m) {
              c.users = get<int>(cfg, "users", c.users);
              c.threads = get<int>(cfg, "threads", c.threads);
              c.max_requests = get<int64_t>(cfg, "max_requests", c.max_requests);
+             c.keep_bodies = get<bool>(cfg, "keep_bodies", c.keep_bodies);
              std::vector<std::string> reqs;
              for (auto r : requests) reqs.push_back(r.cast<std::string>());
              return new HttpLoadGen(c, std::move(reqs));
@@ -992,6 +1004,8 @@ PYBIND11_MODULE(_C, m) {
           py::arg("timeout_s") = 30.0)
       .def("completed", &HttpLoadGen::completed)
       .def("connect_failures", &HttpLoadGen::connect_failures)
+      .def("capture_until", &HttpLoadGen::capture_until, py::arg("n"))
+      .def("bodies", [bodies_py](HttpLoadGen& g) { return bodies_py(g.bodies()); })
       .def(
           "wait_completed",
           [](HttpLoadGen& g, int64_t n, double timeout_s) {
@@ -1057,6 +1071,9 @@ PYBIND11_MODULE(_C, m) {
           },
           py::arg("timeout_s") = 30.0)
       .def("completed", &LocalLoadGen::completed)
+      .def("keep_bodies", &LocalLoadGen::keep_bodies)
+      .def("capture_until", &LocalLoadGen::capture_until, py::arg("n"))
+      .def("bodies", [bodies_py](LocalLoadGen& g) { return bodies_py(g.bodies()); })
       .def(
           "wait_completed",
           [](LocalLoadGen& g, int64_t n, double timeout_s) {

@@ -1125,7 +1125,8 @@ void LocalLoadGen::issue() {
   const int64_t k = next_.fetch_add(1);
   in_flight_.fetch_add(1);
   const auto t_send = Clock::now();
-  fe_->submit_local(uploads_[(size_t)(k % (int64_t)uploads_.size())], [this, t_send](int code, const std::string& body) {
+  const size_t req = (size_t)(k % (int64_t)uploads_.size());
+  fe_->submit_local(uploads_[req], [this, t_send, req](int code, const std::string& body) {
     LoadGenRecord r;
     const auto now = Clock::now();
     r.t_done = std::chrono::duration<double>(now - t0_).count();
@@ -1136,6 +1137,7 @@ void LocalLoadGen::issue() {
     r.dets = (int16_t)n;
     {
       std::lock_guard<std::mutex> lk(mu_);
+      if (keep_bodies_) cap_.put(req, (int64_t)recs_.size(), body.data(), body.size());
       recs_.push_back(r);
     }
     cv_.notify_all();
@@ -1166,6 +1168,22 @@ int64_t LocalLoadGen::completed() {
 bool LocalLoadGen::wait_completed(int64_t n, double timeout_s) {
   std::unique_lock<std::mutex> lk(mu_);
   return cv_.wait_for(lk, std::chrono::duration<double>(timeout_s), [&] { return (int64_t)recs_.size() >= n; });
+}
+
+void LocalLoadGen::keep_bodies() {
+  std::lock_guard<std::mutex> lk(mu_);
+  keep_bodies_ = true;
+  cap_.init(uploads_.size());
+}
+
+void LocalLoadGen::capture_until(int64_t n) {
+  std::lock_guard<std::mutex> lk(mu_);
+  cap_.limit = n;
+}
+
+BodyCapture LocalLoadGen::bodies() {
+  std::lock_guard<std::mutex> lk(mu_);
+  return cap_;
 }
 
 std::vector<LoadGenRecord> LocalLoadGen::records(int64_t from, int64_t to) {

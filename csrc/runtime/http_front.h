@@ -157,6 +157,10 @@ class LocalLoadGen {
   int64_t completed();
   bool wait_completed(int64_t n, double timeout_s);
   std::vector<LoadGenRecord> records(int64_t from, int64_t to);
+  // the latest response body per upload (BodyCapture, http_loadgen.h); keep_bodies() before start()
+  void keep_bodies();
+  void capture_until(int64_t n);
+  BodyCapture bodies();
 
  private:
   void issue();
@@ -169,6 +173,8 @@ class LocalLoadGen {
   std::mutex mu_;
   std::condition_variable cv_;
   std::vector<LoadGenRecord> recs_;
+  bool keep_bodies_ = false;
+  BodyCapture cap_;
 };
 
 class HttpFrontEnd {

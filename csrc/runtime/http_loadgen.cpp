@@ -38,6 +38,7 @@ int count_of(const std::string& s, size_t from, size_t to, const char* pat) {
 struct HttpLoadGen::Conn {
   int fd = -1;
   const std::string* out = nullptr;  // request being sent
+  size_t req = 0;                    // its index in reqs_
   size_t off = 0;
   std::string in;
   double t_send = 0;
@@ -49,6 +50,7 @@ HttpLoadGen::HttpLoadGen(LoadGenConfig cfg, std::vector<std::string> requests)
   if (reqs_.empty()) throw std::runtime_error("HttpLoadGen: no requests");
   if (cfg_.users < 1) throw std::runtime_error("HttpLoadGen: users < 1");
   cfg_.threads = std::max(1, std::min(cfg_.threads, cfg_.users));
+  if (cfg_.keep_bodies) cap_.init(reqs_.size());
 }
 
 HttpLoadGen::~HttpLoadGen() { stop(0.0); }
@@ -109,7 +111,8 @@ void HttpLoadGen::loop(int idx) {
     if (!issuing_.load()) return false;
     const int64_t k = next_req_.fetch_add(1);
     if (cfg_.max_requests > 0 && k >= cfg_.max_requests) return false;
-    c->out = &reqs_[(size_t)(k % (int64_t)reqs_.size())];
+    c->req = (size_t)(k % (int64_t)reqs_.size());
+    c->out = &reqs_[c->req];
     c->off = 0;
     c->in.clear();
     c->t_send = now_s();
@@ -117,11 +120,12 @@ void HttpLoadGen::loop(int idx) {
     in_flight_.fetch_add(1);
     return true;
   };
-  auto record = [&](Conn* c, int status, int dets) {
+  auto record = [&](Conn* c, int status, int dets, size_t body = 0, size_t body_len = 0) {
     c->waiting = false;
     {
       std::lock_guard<std::mutex> lk(mu_);
       const double t = now_s();  // under the lock: records are in completion order across threads
+      if (cfg_.keep_bodies && status > 0) cap_.put(c->req, (int64_t)recs_.size(), c->in.data() + body, body_len);
       recs_.push_back({t - t0_, (float)(t - c->t_send), (int16_t)status, (int16_t)std::min(dets, 32767)});
     }
     in_flight_.fetch_sub(1);
@@ -218,7 +222,7 @@ void HttpLoadGen::loop(int idx) {
         }
         const size_t total = hend + 4 + (size_t)std::max<int64_t>(0, clen);
         if (c->in.size() < total) break;
-        record(c, status, count_of(c->in, hend + 4, total, "\"class_name\""));
+        record(c, status, count_of(c->in, hend + 4, total, "\"class_name\""), hend + 4, total - (hend + 4));
         c->in.erase(0, total);
         if (close_after) {
           broken = true;
@@ -270,6 +274,16 @@ bool HttpLoadGen::wait_completed(int64_t n, double timeout_s) {
       return false;
   }
   return true;
+}
+
+void HttpLoadGen::capture_until(int64_t n) {
+  std::lock_guard<std::mutex> lk(mu_);
+  cap_.limit = n;
+}
+
+BodyCapture HttpLoadGen::bodies() {
+  std::lock_guard<std::mutex> lk(mu_);
+  return cap_;
 }
 
 std::vector<LoadGenRecord> HttpLoadGen::records(int64_t from, int64_t to) {

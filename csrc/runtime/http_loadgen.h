@@ -22,6 +22,25 @@ struct LoadGenConfig {
   int users = 1;
   int threads = 1;
   int64_t max_requests = 0;  // stop issuing after this many (0 = until stop())
+  bool keep_bodies = false;  // keep the latest response body of every distinct request (bodies())
+};
+
+// The latest response body per distinct request (opt-in: bench.py --dump-outputs).  Completion k's body
+// replaces the one stored for its request while k < the limit, so a limit at the end of the timed window
+// leaves what the window's requests were answered with.  Guarded by the owner's record mutex.
+struct BodyCapture {
+  std::vector<std::string> body;  // by request index; empty until answered
+  std::vector<int64_t> at;        // completion index of the stored body, -1: none
+  int64_t limit = INT64_MAX;
+  void init(size_t n) {
+    body.assign(n, std::string());
+    at.assign(n, -1);
+  }
+  void put(size_t req, int64_t k, const char* p, size_t n) {
+    if (k >= limit || req >= body.size()) return;
+    body[req].assign(p, n);
+    at[req] = k;
+  }
 };
 
 struct LoadGenRecord {
@@ -46,6 +65,9 @@ class HttpLoadGen {
   bool wait_completed(int64_t n, double timeout_s);
   std::vector<LoadGenRecord> records(int64_t from, int64_t to);
   int64_t connect_failures() const { return connect_failures_.load(); }
+  // keep_bodies: completions from index n on are no longer stored / a copy of what is stored
+  void capture_until(int64_t n);
+  BodyCapture bodies();
 
   struct Conn;
 
@@ -64,6 +86,7 @@ class HttpLoadGen {
   std::mutex mu_;
   std::condition_variable cv_;
   std::vector<LoadGenRecord> recs_;
+  BodyCapture cap_;
 };
 
 }  // namespace arena

@@ -9,5 +9,8 @@ timeout -k 10 600 python -m pytest tests -m gpu -q -p no:cacheprovider > gpurun_
 tail -3 gpurun_out/pytest_gpu.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1
 tail -2 gpurun_out/smoke.log
-timeout -k 10 600 python bench.py --steps ${STEPS:-100} --warmup 10 > gpurun_out/bench.json 2> gpurun_out/bench.err
-cat gpurun_out/bench.json
+# --full: the record keeps the engine-only rates, the 1/10/100-user levels, the in-process and bf16 windows
+BENCH_OUT=${BENCH_OUT:-bench_out}
+mkdir -p "$BENCH_OUT"
+timeout -k 10 600 python bench.py --full --steps ${STEPS:-100} --warmup 10 > "$BENCH_OUT/bench.json" 2> "$BENCH_OUT/bench.err"
+cat "$BENCH_OUT/bench.json"

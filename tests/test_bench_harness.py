@@ -22,7 +22,7 @@ def _bench(*args, env=None):
 
 
 def test_bench_two_ranks_self_launch_http():
-    r = _bench("--gpus", "2", "--latency-levels", "1,4")
+    r = _bench("--gpus", "2", "--full", "--latency-levels", "1,4")
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["n_gpus"] == 2 and out["world_size_checked"] == 2 and out["config"]["parallelism"] == "dp2"
@@ -38,6 +38,33 @@ def test_bench_two_ranks_self_launch_http():
     # the per-request host CPU breakdown: every upload went through the native split decoder
     assert out["stage_cpu_us_per_req"]["native_decoded"] >= 2 * 256 and out["stage_cpu_us_per_req"]["fallback_decoded"] == 0
     assert out["host_cpu_us_per_req"]["total"] > 0 and out["host_cpu_us_per_req"]["decode"] > 0
+
+
+def test_bench_plain_run_measures_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without --full nothing but the headline window runs; --dump-outputs writes what the window's clients
+    received, row i = upload i, the same arrays on every run with the same arguments."""
+    import numpy as np
+
+    dumps = []
+    for name in ("a", "b"):
+        r = _bench("--gpus", "1", "--dump-outputs", str(tmp_path / name))
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert out["steps"] == 2 and out["errors"] == 0 and out["value"] > 0
+        assert out["ms_per_step"] * out["steps"] / 1e3 == pytest.approx(2 * 256 / out["value"], rel=1e-3)
+        assert out["levels"] == {} and out["bs1_p50_ms"] is None and out["engine_req_s"] is None
+        assert "inproc" not in out and "bf16" not in out and "shared_front" not in out
+        assert "level " not in r.stderr
+        files = sorted(p.name for p in (tmp_path / name).iterdir())
+        assert files == sorted(f"{k}.npy" for k in out["dumped_outputs"]["arrays"])
+        dumps.append({p.stem: np.load(p) for p in (tmp_path / name).iterdir()})
+    a, b = dumps
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["answered"].shape == (16,) and a["answered"].all()  # the fake engine's 16 uploads, all in the window
+    assert (a["num_detections"] > 0).all() and a["boxes"].shape[0] == 16 and a["boxes"].shape[2] == 4
+    assert (a["boxes"][:, 0, 2] > a["boxes"][:, 0, 0]).all()
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
 
 
 def test_bench_shared_front_headline():
