@@ -17,6 +17,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace arena {
 
@@ -61,6 +62,22 @@ __device__ __forceinline__ uint2 pack4(const float* f) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) v[i] = (bf16)f[i];
   return __builtin_bit_cast(uint2, v);
+}
+
+// Triple-bf16 split of two floats at once: v = h + m + l with h = bf16(v), m = bf16(v - h), l = bf16(v - h - m)
+// (the operand planes of the fp32-accurate MFMA kernels).  Bit-identical to the element-wise form
+//   th = (bf16)v; r = v - (float)th; tm = (bf16)r; l = (bf16)(r - (float)tm)
+// but 10 VALU per pair instead of 12-13: one v_cvt_pk_bf16_f32 converts both values, the packed word is widened
+// back with one shift (low half) and one mask (high half), and the residual is one v_pk_add_f32.
+__device__ __forceinline__ f32x2 widen_bf16x2(bf16x2 v) {
+  const unsigned u = __builtin_bit_cast(unsigned, v);
+  return f32x2{__builtin_bit_cast(float, u << 16), __builtin_bit_cast(float, u & 0xffff0000u)};
+}
+__device__ __forceinline__ void split_bf16x3_pair(f32x2 v, bf16x2& h, bf16x2& m, bf16x2& l) {
+  h = __builtin_convertvector(v, bf16x2);
+  const f32x2 r = v - widen_bf16x2(h);
+  m = __builtin_convertvector(r, bf16x2);
+  l = __builtin_convertvector(r - widen_bf16x2(m), bf16x2);
 }
 
 // 8 consecutive elements of an NHWC row as fp32, for kernels templated on the

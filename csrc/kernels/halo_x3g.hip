@@ -263,21 +263,13 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_x3hg_kernel(const ConvParam
     for (int j = 0; j < XI; ++j) {
       const int i = tid + NT * j;
       if (HPIX * 4 % NT == 0 || i < HPIX * 4) {
-        bf16x4 h, m, l;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float v = rx[j][e];
-          const bf16 th = (bf16)v;
-          const float r = v - (float)th;
-          const bf16 tm = (bf16)r;
-          h[e] = th;
-          m[e] = tm;
-          l[e] = (bf16)(r - (float)tm);
-        }
+        bf16x2 h0, m0, l0, h1, m1, l1;  // split two values at a time (common.h)
+        split_bf16x3_pair(f32x2{rx[j][0], rx[j][1]}, h0, m0, l0);
+        split_bf16x3_pair(f32x2{rx[j][2], rx[j][3]}, h1, m1, l1);
         bf16* d = sX + (i >> 2) * HG_P + 4 * (i & 3);
-        *(bf16x4*)d = h;
-        *(bf16x4*)(d + 16) = m;
-        *(bf16x4*)(d + 32) = l;
+        *(bf16x4*)d = __builtin_shufflevector(h0, h1, 0, 1, 2, 3);
+        *(bf16x4*)(d + 16) = __builtin_shufflevector(m0, m1, 0, 1, 2, 3);
+        *(bf16x4*)(d + 32) = __builtin_shufflevector(l0, l1, 0, 1, 2, 3);
       }
     }
   };

@@ -277,16 +277,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(S == 2 && K
       float4 v[9];
 #pragma unroll
       for (int t = 0; t < 9; ++t) v[t] = *(const float4*)&E[addr[t]];
-      float4 a = bdw;
+      // channel pairs on v_pk_fma_f32: each lane rounds like fmaf, the tap order is unchanged (block 2 at 112x112,
+      // per batch of 32 requests: 221.1 -> 215.8 us, SQ_INSTS_VALU 4.38e7 -> 4.08e7; profiles/r7_dw_strips)
+      f32x2 a0 = {bdw.x, bdw.y}, a1 = {bdw.z, bdw.w};
 #pragma unroll
       for (int t = 0; t < 9; ++t) {
         const float4 w = wk[t];
-        a.x = fmaf(v[t].x, w.x, a.x);
-        a.y = fmaf(v[t].y, w.y, a.y);
-        a.z = fmaf(v[t].z, w.z, a.z);
-        a.w = fmaf(v[t].w, w.w, a.w);
+        a0 = __builtin_elementwise_fma(f32x2{v[t].x, v[t].y}, f32x2{w.x, w.y}, a0);
+        a1 = __builtin_elementwise_fma(f32x2{v[t].z, v[t].w}, f32x2{w.z, w.w}, a1);
       }
-      *(float4*)&Ds[q * IRF_DP + 4 * g] = relu6x4(a);
+      *(float4*)&Ds[q * IRF_DP + 4 * g] = relu6x4(make_float4(a0[0], a0[1], a1[0], a1[1]));
     }
     __syncthreads();
     // next chunk's expand / depthwise weights, in flight during the project GEMM (unconditional: a conditional

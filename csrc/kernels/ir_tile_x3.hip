@@ -14,6 +14,16 @@
 //   D = relu6(dw3x3_S(E) + bd)                                    -> split, bf16 planes in LDS
 //   acc += Wp[:, chunk] . D                                       registers for the whole chunk loop
 //   y = acc + bp (+ x)
+// Depthwise phase (two thirds of the kernel's VALU instructions before): at stride 1 every thread computes a
+// vertical strip of four outputs from 18 LDS reads whose six addresses are computed once per kernel (ItxStrip; it
+// was four passes of 9 reads and 9 addresses each, per hidden chunk); at both strides the taps are v_pk_fma_f32 on
+// channel pairs and the D split converts two values at a time (common.h split_bf16x3_pair).  Tap order and
+// rounding per output are unchanged, so results are bit-identical to the scalar form.  Measured per batch of 32
+// requests, same box, before -> after (profiles/r7_dw_strips): <1, 8, 16, 2, 1> at 56x56 182.3 -> 149.6 us and at
+// 28x28 71.4 -> 61.0 us, SQ_INSTS_VALU 5.73e7 -> 3.74e7 and SQ_INSTS_LDS 5.81e6 -> 4.37e6 (56x56), bank-conflict
+// cycles unchanged (the removed reads were conflict-free); ir_stem_x3_kernel 175.8 -> 161.1 us, VALU 7.10e7 ->
+// 5.88e7, LDS 3.94e6 -> 2.93e6; the stride-2 tiles (packed FMAs and pair split only) 105.4 -> 97.8 and 44.6 ->
+// 43.7 us.
 // Weights: the x3w planes the planner packs for these blocks (engine/planner.py split_bf16x3): we bf16
 // [hid_pad][3][inp_pad], wp bf16 [oup_pad][3][hid_pad]; wd fp32 [9][hid_pad]; biases fp32.
 #include <cstdlib>
@@ -41,30 +51,102 @@ __device__ __forceinline__ int itx_eswz(int pix, int g) {
   return (g & ~7) | ((g & 7) ^ f);
 }
 
+// v = h + m + l planes of 8 / 4 values, two at a time (common.h split_bf16x3_pair)
 __device__ __forceinline__ void itx_split8(const float* v, bf16x8& h, bf16x8& m, bf16x8& l) {
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const bf16 th = (bf16)v[i];
-    const float r = v[i] - (float)th;
-    const bf16 tm = (bf16)r;
-    h[i] = th;
-    m[i] = tm;
-    l[i] = (bf16)(r - (float)tm);
+  for (int i = 0; i < 8; i += 2) {
+    bf16x2 th, tm, tl;
+    split_bf16x3_pair(f32x2{v[i], v[i + 1]}, th, tm, tl);
+    h[i] = th[0]; h[i + 1] = th[1];
+    m[i] = tm[0]; m[i + 1] = tm[1];
+    l[i] = tl[0]; l[i + 1] = tl[1];
   }
 }
 
-__device__ __forceinline__ void itx_split4(const float4 v, bf16x4& h, bf16x4& m, bf16x4& l) {
-  const float a[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const bf16 th = (bf16)a[i];
-    const float r = a[i] - (float)th;
-    const bf16 tm = (bf16)r;
-    h[i] = th;
-    m[i] = tm;
-    l[i] = (bf16)(r - (float)tm);
-  }
+__device__ __forceinline__ void itx_split4(f32x2 v0, f32x2 v1, bf16x4& h, bf16x4& m, bf16x4& l) {
+  bf16x2 h0, m0, l0, h1, m1, l1;
+  split_bf16x3_pair(v0, h0, m0, l0);
+  split_bf16x3_pair(v1, h1, m1, l1);
+  h = __builtin_shufflevector(h0, h1, 0, 1, 2, 3);
+  m = __builtin_shufflevector(m0, m1, 0, 1, 2, 3);
+  l = __builtin_shufflevector(l0, l1, 0, 1, 2, 3);
 }
+
+// Depthwise accumulator of one output pixel's 4 channels as two channel pairs: every tap is two v_pk_fma_f32
+// (each lane rounds like fmaf, so the result is that of the scalar chain bias, tap 0, .. tap 8).
+struct ItxDw {
+  f32x2 a0, a1;
+  __device__ __forceinline__ explicit ItxDw(const float4 b) : a0{b.x, b.y}, a1{b.z, b.w} {}
+  __device__ __forceinline__ void tap(const float4 v, const float4 w) {
+    a0 = __builtin_elementwise_fma(f32x2{v.x, v.y}, f32x2{w.x, w.y}, a0);
+    a1 = __builtin_elementwise_fma(f32x2{v.z, v.w}, f32x2{w.z, w.w}, a1);
+  }
+  // ReLU6, split, the three bf16 planes of D (d: the pixel's row + 8 * channel group)
+  __device__ __forceinline__ void store(uint8_t* d) const {
+    bf16x4 dh, dm, dl;
+    itx_split4(f32x2{relu6f(a0[0]), relu6f(a0[1])}, f32x2{relu6f(a1[0]), relu6f(a1[1])}, dh, dm, dl);
+    *(bf16x4*)d = dh;
+    *(bf16x4*)(d + 64) = dm;
+    *(bf16x4*)(d + 128) = dl;
+  }
+};
+
+// Stride-1 depthwise on the 8 x 16 tile: thread (pixel item pi = tid >> 3, channel group g) owns the vertical
+// strip of four outputs (ox = pi & 15, oy = 4 (pi >> 4) .. + 3).  It reads the strip's 6 rows x 3 columns of the
+// source map once (18 ds_read_b128, against 36 when the four outputs were four loop passes re-reading 6 of their
+// 9 taps).  Within every read instruction the lanes still cover 8 consecutive pixels of one row x 8 channel groups,
+// as before, so the swizzle serves them the same way (SQ_LDS_BANK_CONFLICT of these ops did not change).
+// The swizzle term of a pixel depends on px & 3 only ((px ^ 4 (px >> 2)) & 7 == px & 3), and two halo rows are
+// 2 PW = 36 pixels apart: rows r and r + 2 differ by a constant, so six addresses (rows 0 / 1 x 3 columns),
+// computed once per kernel, serve all 18 reads through the instruction's immediate offset.
+constexpr int ITX_SW = 16, ITX_SPW = ITX_SW + 2;  // strip kernels: tile and halo width
+static_assert((2 * ITX_SPW) % 4 == 0, "rows r and r + 2 must share their swizzle term");
+
+template <int EP>
+struct ItxStrip {
+  int a[2][3];  // float index of halo pixel (row 4 s + r, column ox + c), r = 0 / 1, for channel group g
+  int q0;       // first output pixel of the strip
+  __device__ __forceinline__ ItxStrip(int tid, int g) {
+    const int pi = tid >> 3;
+    const int ox = pi & (ITX_SW - 1), oyb = 4 * (pi / ITX_SW);
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int px = (oyb + r) * ITX_SPW + ox + c;
+        a[r][c] = px * EP + 4 * itx_eswz<1>(px, g);
+      }
+    q0 = oyb * ITX_SW + ox;
+  }
+  // D rows q0 + 16 j, j = 0..3, from the map E with the taps wk and bias bdw of this thread's 4 channels
+  __device__ __forceinline__ void run(const float* E, uint8_t* Ds, int g, const float4 (&wk)[9], const float4 bdw) const {
+    // Rows are consumed in order: row r feeds taps 3 (r - j) .. + 2 of output j = r - 2 .. r, so every output still
+    // accumulates bias, tap 0, .. tap 8.  Rows 0 and 1 are requested up front and row r + 2 once row r is consumed,
+    // so a row's round trip is covered by the 6..18 packed FMAs and the output split of the row before it.  The
+    // tiled kernel already sits at the 256 registers of its occupancy (2 workgroups per CU, set by LDS): with all
+    // 18 reads, or four rows of them, issued ahead of the first FMA the <1, 8, 16, 2, 1> instance spilled.
+    float4 v[6][3];
+    auto load_row = [&](int r) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) v[r][c] = *(const float4*)&E[a[r & 1][c] + (r >> 1) * 2 * ITX_SPW * EP];
+    };
+#pragma unroll
+    for (int r = 0; r < 2; ++r) load_row(r);
+    ItxDw dw[4] = {ItxDw(bdw), ItxDw(bdw), ItxDw(bdw), ItxDw(bdw)};
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int ky = r - j;
+        if (ky < 0 || ky > 2) continue;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) dw[j].tap(v[r][c], wk[3 * ky + c]);
+        if (ky == 2) dw[j].store(Ds + (q0 + ITX_SW * j) * ITX_DPB + 8 * g);
+      }
+      if (r < 4) load_row(r + 2);
+    }
+  }
+};
 
 __device__ __forceinline__ f32x4 itx_mfma(const bf16x8& ah, const bf16x8& am, const bf16x8& al, const bf16x8& bh,
                                           const bf16x8& bm, const bf16x8& bl, f32x4 c) {
@@ -177,6 +259,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KS == 1 ? 2
     *(float4*)&Wd[r * hid_pad + 4 * c4] = *(const float4*)(src + 4 * c4);
   }
   const int g = tid & 7;  // depthwise channel group (4 channels) of this thread
+  // the strips' read addresses do not depend on the chunk: computed here, once
+  static_assert(S == 2 || (TH == 8 && TW == ITX_SW), "stride 1 runs the 8 x 16 strip form");
+  const ItxStrip<EP> strip(tid, g);  // S == 1 (unused, and removed, at S == 2)
   load_expand(0, wexp, bexp);
   load_project(0, wprj);
 
@@ -211,13 +296,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KS == 1 ? 2
 #pragma unroll
       for (int k = 0; k < 9; ++k) wk[k] = *(const float4*)&Wd[k * hid_pad + h0 + 4 * g];
       const float4 bdw = *(const float4*)&Wd[9 * hid_pad + h0 + 4 * g];
-      static_assert(POUT % 32 == 0, "depthwise: whole passes of 32 pixels");
-      // all nine taps' LDS reads of a pixel are issued before its FMAs (one address each, computed up front):
-      // with the reads interleaved into the FMA chain the compiler reused one register set and waited for
-      // every read in turn (nine serialised LDS round trips per pixel)
-#pragma unroll 1
-      for (int qi = 0; qi < POUT / 32; ++qi) {  // not unrolled: 36 tap addresses would stay live over the chunk loop
-        const int q = (tid >> 3) + 32 * qi;
+      if constexpr (S == 1) {
+        strip.run(Es, Ds, g, wk, bdw);
+      } else {
+        // one output pixel per thread; all nine taps' LDS reads are issued before its FMAs (one address each,
+        // computed up front): with the reads interleaved into the FMA chain the compiler reused one register
+        // set and waited for every read in turn (nine serialised LDS round trips per pixel)
+        static_assert(POUT == 32, "stride 2: one pass of 32 pixels");
+        const int q = tid >> 3;
         const int oy = q / TW, ox = q - oy * TW;
         int addr[9];
 #pragma unroll
@@ -228,21 +314,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KS == 1 ? 2
         float4 v[9];
 #pragma unroll
         for (int t = 0; t < 9; ++t) v[t] = *(const float4*)&Es[addr[t]];
-        float4 a = bdw;
+        ItxDw dw(bdw);
 #pragma unroll
-        for (int t = 0; t < 9; ++t) {
-          const float4 w = wk[t];
-          a.x = fmaf(v[t].x, w.x, a.x);
-          a.y = fmaf(v[t].y, w.y, a.y);
-          a.z = fmaf(v[t].z, w.z, a.z);
-          a.w = fmaf(v[t].w, w.w, a.w);
-        }
-        bf16x4 dh, dm, dl;
-        itx_split4(itx_relu6x4(a), dh, dm, dl);
-        uint8_t* d = Ds + q * ITX_DPB + 8 * g;
-        *(bf16x4*)d = dh;
-        *(bf16x4*)(d + 64) = dm;
-        *(bf16x4*)(d + 128) = dl;
+        for (int t = 0; t < 9; ++t) dw.tap(v[t], wk[t]);
+        dw.store(Ds + q * ITX_DPB + 8 * g);
       }
     }
     __syncthreads();
@@ -434,35 +509,9 @@ __global__ __launch_bounds__(256) void ir_stem_x3_kernel(const IrParams p) {
 
   // ---- depthwise 3x3 on X (t = 1: X is the hidden map) + bias + ReLU6 -> split planes of D
   {
-#pragma unroll 1
-    for (int qi = 0; qi < POUT / 32; ++qi) {  // reads issued ahead of the FMAs, as in ir_tile_x3_kernel
-      const int q = (tid >> 3) + 32 * qi;
-      const int oy = q / TW, ox = q - oy * TW;
-      int addr[9];
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        const int px = (oy + t / 3) * PW + ox + t % 3;
-        addr[t] = px * XP + 4 * itx_eswz<S>(px, g);
-      }
-      float4 v[9];
-#pragma unroll
-      for (int t = 0; t < 9; ++t) v[t] = *(const float4*)&Xs[addr[t]];
-      float4 a = bdw;
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        const float4 w = wk[t];
-        a.x = fmaf(v[t].x, w.x, a.x);
-        a.y = fmaf(v[t].y, w.y, a.y);
-        a.z = fmaf(v[t].z, w.z, a.z);
-        a.w = fmaf(v[t].w, w.w, a.w);
-      }
-      bf16x4 dh, dm, dl;
-      itx_split4(itx_relu6x4(a), dh, dm, dl);
-      uint8_t* d = Ds + q * ITX_DPB + 8 * g;
-      *(bf16x4*)d = dh;
-      *(bf16x4*)(d + 64) = dm;
-      *(bf16x4*)(d + 128) = dl;
-    }
+    static_assert(TH == 8 && TW == ITX_SW && PW == ITX_SPW, "the 8 x 16 strip form");
+    const ItxStrip<XP> strip(tid, g);  // vertical strips of four outputs, as in ir_tile_x3_kernel
+    strip.run(Xs, Ds, g, wk, bdw);
   }
   __syncthreads();
 
