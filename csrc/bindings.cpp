@@ -473,7 +473,7 @@ std::vector<InputImage> images_from(const py::list& imgs, std::vector<py::array>
         st = jpeg_decode_coefs((const uint8_t*)data.data(), data.size(), jh->info, jh->coef.data(), err);
       }
       if (st != JpegStatus::Ok) throw py::value_error("JPEG input not decodable by the split decoder: " + err);
-      InputImage im{(const uint8_t*)jh->coef.data(), jh->info.height, jh->info.width};
+      InputImage im{(const uint8_t*)jh->coef.data(), jh->info.out_height, jh->info.out_width};
       im.jpeg = &jh->info;
       jkeep->push_back(jh);
       v.push_back(im);
@@ -660,7 +660,7 @@ PYBIND11_MODULE(_C, m) {
              for (int i : idx) {
                if (i < 0 || i >= (int)set->items.size()) throw py::index_error("submit_jpeg_set: index out of range");
                const auto& it = set->items[i];
-               InputImage im{(const uint8_t*)it->coef, it->info.height, it->info.width};
+               InputImage im{(const uint8_t*)it->coef, it->info.out_height, it->info.out_width};
                im.jpeg = &it->info;
                v.push_back(im);
              }
@@ -1199,6 +1199,7 @@ PYBIND11_MODULE(_C, m) {
              d["sum_gpu_ms"] = s.sum_gpu_ms;
              d["native_decoded"] = s.native_decoded;
              d["fallback_decoded"] = s.fallback_decoded;
+             d["oriented_decoded"] = s.oriented_decoded;
              d["bodies_recycled"] = s.bodies_recycled;
              d["bodies_allocated"] = s.bodies_allocated;
              d["cpu_parse_ms"] = s.cpu_parse_ms;

@@ -32,6 +32,9 @@ py::dict info_dict(const JpegInfo& in) {
   d["height"] = in.height;
   d["ncomp"] = in.ncomp;
   d["layout"] = in.layout;
+  d["orientation"] = in.orientation;
+  d["out_width"] = in.out_width;
+  d["out_height"] = in.out_height;
   d["mcux"] = in.mcux;
   d["mcuy"] = in.mcuy;
   d["restart_interval"] = in.restart_interval;
@@ -116,28 +119,36 @@ void bind_jpeg(py::module& m) {
           }
         }
         if (st != JpegStatus::Ok) return py::make_tuple(status_name(st), err, py::none());
-        py::array_t<uint8_t> a({(py::ssize_t)p.info.height, (py::ssize_t)p.info.width, (py::ssize_t)3});
+        py::array_t<uint8_t> a({(py::ssize_t)p.info.out_height, (py::ssize_t)p.info.out_width, (py::ssize_t)3});
         std::memcpy(a.mutable_data(), rgb.data(), rgb.size());
         return py::make_tuple("ok", std::string(), a);
       },
       py::arg("data"), py::arg("max_pixels") = 0,
-      "Whole decode on the host with the device kernels' arithmetic: (status, error, HxWx3 uint8 or None).");
+      "Whole decode on the host with the device kernels' arithmetic: (status, error, HxWx3 uint8 in the EXIF\n"
+      "orientation, or None).");
 
   m.def(
       "jpeg_decode_device",
-      [](std::vector<py::bytes> uploads, int device) {
+      [](std::vector<py::bytes> uploads, int device, bool guard) {
         const int n = (int)uploads.size();
         std::vector<Parsed> ps(n);
         std::vector<JpegDesc> descs(n);
         int64_t off = 0, max_blocks = 0, max_pix = 0;
+        bool oriented = false;
+        // guard: kGuard bytes of kGuardByte right before and right after every RGB region (not rounded up to the
+        // pool's alignment, so one byte past the frame already lands in them), checked after the kernels
+        constexpr int64_t kGuard = 256;
+        constexpr int kGuardByte = 0xA5;
         std::vector<int64_t> coef_base(n), rgb_off(n);
         for (int i = 0; i < n; ++i) {
           std::string err;
           const std::string s = uploads[i];
           if (parse_decode(s, ps[i], err, 0) != JpegStatus::Ok) throw std::invalid_argument("upload " + std::to_string(i) + ": " + err);
           const JpegInfo& in = ps[i].info;
+          if (guard) off += kGuard;
           rgb_off[i] = off;
-          off = align256(off + (int64_t)in.width * in.height * 3);
+          off = align256(off + (int64_t)in.width * in.height * 3 + (guard ? kGuard : 0));
+          oriented |= in.orientation > 1;
           coef_base[i] = off;
           off = align256(off + in.coef_count * 2);
           descs[i] = jpeg_device_desc(in, coef_base[i], off, rgb_off[i]);
@@ -158,12 +169,25 @@ void bind_jpeg(py::module& m) {
           for (int i = 0; i < n; ++i)
             check(hipMemcpy(pool + coef_base[i], ps[i].coef.data(), ps[i].coef.size() * 2, hipMemcpyHostToDevice), "H2D coef");
           check(hipMemcpy(dd, descs.data(), sizeof(JpegDesc) * n, hipMemcpyHostToDevice), "H2D desc");
-          jpeg_reconstruct(dd, pool, n, (int)max_blocks, max_pix, nullptr);
+          if (guard)
+            for (int i = 0; i < n; ++i) {
+              check(hipMemset(pool + rgb_off[i] - kGuard, kGuardByte, (size_t)kGuard), "guard");
+              check(hipMemset(pool + rgb_off[i] + (int64_t)ps[i].info.width * ps[i].info.height * 3, kGuardByte, (size_t)kGuard), "guard");
+            }
+          jpeg_reconstruct(dd, pool, n, (int)max_blocks, max_pix, nullptr, oriented);
           check(hipGetLastError(), "jpeg_reconstruct launch");
           check(hipDeviceSynchronize(), "jpeg_reconstruct");
           for (int i = 0; i < n; ++i) {
             rgb[i].resize((size_t)ps[i].info.width * ps[i].info.height * 3);
             check(hipMemcpy(rgb[i].data(), pool + rgb_off[i], rgb[i].size(), hipMemcpyDeviceToHost), "D2H rgb");
+            if (!guard) continue;
+            uint8_t g[2 * kGuard];
+            check(hipMemcpy(g, pool + rgb_off[i] - kGuard, (size_t)kGuard, hipMemcpyDeviceToHost), "D2H guard");
+            check(hipMemcpy(g + kGuard, pool + rgb_off[i] + (int64_t)rgb[i].size(), (size_t)kGuard, hipMemcpyDeviceToHost), "D2H guard");
+            for (int64_t k = 0; k < 2 * kGuard; ++k)
+              if (g[k] != kGuardByte)
+                throw std::runtime_error("jpeg_decode_device: the kernels wrote " + std::string(k < kGuard ? "before" : "past") +
+                                         " the RGB region of upload " + std::to_string(i));
           }
         } catch (...) {
           hipFree(pool);
@@ -173,14 +197,15 @@ void bind_jpeg(py::module& m) {
         hipFree(pool);
         hipFree(dd);
         for (int i = 0; i < n; ++i) {
-          py::array_t<uint8_t> a({(py::ssize_t)ps[i].info.height, (py::ssize_t)ps[i].info.width, (py::ssize_t)3});
+          py::array_t<uint8_t> a({(py::ssize_t)ps[i].info.out_height, (py::ssize_t)ps[i].info.out_width, (py::ssize_t)3});
           std::memcpy(a.mutable_data(), rgb[i].data(), rgb[i].size());
           out.append(a);
         }
         return out;
       },
-      py::arg("uploads"), py::arg("device") = 0,
-      "Entropy-decode on the host, reconstruct on the GPU (jpeg_idct.hip): list of HxWx3 uint8.");
+      py::arg("uploads"), py::arg("device") = 0, py::arg("guard") = false,
+      "Entropy-decode on the host, reconstruct on the GPU (jpeg_idct.hip): list of HxWx3 uint8 in the EXIF\n"
+      "orientation.  guard=True surrounds each RGB region with guard bytes and raises if the kernels touched them.");
 }
 
 }  // namespace arena

@@ -23,8 +23,9 @@ struct JpegCompDesc {
 struct JpegDesc {
   int32_t ncomp, layout, width, height;
   int32_t total_blocks;  // sum over components of bw * bh
-  int32_t pad_[3];
-  int64_t rgb_off;       // packed HxWx3 RGB output (the ImageMeta offset the pipeline reads)
+  int32_t orientation;   // EXIF orientation 1..8 of the output (0 reads as 1): see jpeg_idct.hip for the placement
+  int32_t pad_[2];
+  int64_t rgb_off;       // packed RGB output in the oriented geometry (the ImageMeta offset the pipeline reads)
   JpegCompDesc comp[kJpegMaxComp];
   uint16_t qt[kJpegMaxComp][64];  // dequantization table per component, natural order
   // compact payload (runtime/jpeg_decode.h jpeg_decode_compact; comp[].coef_off unused): per block a uint64

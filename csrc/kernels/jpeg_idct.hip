@@ -11,6 +11,11 @@
 //                       loaded once per lane, fancy upsampling (h2v2 / h2v1 / none) + YCbCr->RGB, three 4-byte
 //                       stores.  grid (pixels / 1024, images), grid-stride over rows x quads.
 //
+// A batch that holds an image with an EXIF orientation other than 1 launches jpeg_color_oriented_kernel in
+// place of jpeg_color_kernel (the host knows from the descriptors it built); every other batch launches exactly
+// the two kernels above.  The oriented kernel computes each quad with the same color_quad and only places it
+// differently (see its comment), so its pixels are those of the plain kernel, moved.
+//
 // The arithmetic is kernels/jpeg_math.h, the same functions the host reference (jpeg_coefs_to_rgb) uses, so
 // the result is bit-identical to it and to PIL / libjpeg-turbo (tests/test_jpeg_native_gpu.py).  The work is
 // a few MB of traffic per batch of 32 frames: latency, not throughput, is what the layout optimises (every
@@ -142,6 +147,9 @@ __device__ __forceinline__ ChromaRow chroma_row(const uint8_t* __restrict__ row,
 __device__ __forceinline__ int quad_c(int i) { return i < 2 ? 1 : 2; }
 __device__ __forceinline__ int quad_n(int i) { return i == 0 ? 0 : i == 1 ? 2 : i == 2 ? 1 : 3; }
 
+// The kernel of every batch without an EXIF orientation, i.e. of the whole benchmark workload.  It is kept as one
+// self-contained body, so its code object does not move when the oriented kernel below changes; color_quad is the
+// same per-quad code as a function, for the oriented kernel.
 __global__ __launch_bounds__(256) void jpeg_color_kernel(const JpegDesc* __restrict__ descs, uint8_t* __restrict__ pool) {
   const JpegDesc& d = descs[blockIdx.y];
   const int W = d.width, H = d.height, layout = d.layout;
@@ -205,16 +213,217 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const JpegDesc* __restr
   }
 }
 
+// RGB of the quad q of source row y (px: 4 pixels x 3 bytes).  All four pixels are computed whatever the width:
+// the luma dword lies inside the plane's 8-sample padded row and the chroma columns are clamped.
+__device__ __forceinline__ void color_quad(const JpegDesc& d, const uint8_t* __restrict__ pool,
+                                           const uint8_t* __restrict__ yp, int ys, int layout, int y, int q,
+                                           uint8_t* px) {
+  const int x0 = 4 * q;
+  const uint32_t yw = *reinterpret_cast<const uint32_t*>(yp + (int64_t)y * ys + x0);
+  if (layout == JPEG_GRAY) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) px[3 * i] = px[3 * i + 1] = px[3 * i + 2] = (uint8_t)(yw >> (8 * i));
+  } else {
+    int cb[4], cr[4];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const JpegCompDesc& C = d.comp[1 + k];
+      const uint8_t* cp = pool + C.plane_off;
+      const int cs = C.bw * 8;
+      int* dst = k == 0 ? cb : cr;
+      if (layout == JPEG_444) {
+        const uint32_t w = *reinterpret_cast<const uint32_t*>(cp + (int64_t)y * cs + x0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dst[i] = (int)((w >> (8 * i)) & 0xFF);
+      } else if (layout == JPEG_422) {
+        const ChromaRow r = chroma_row(cp + (int64_t)y * cs, 2 * q, C.cw);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dst[i] = jpegm::fancy_h2v1(r.v[quad_c(i)], r.v[quad_n(i)], i & 1);
+      } else {
+        const int cy = y >> 1;
+        const int ny = (y & 1) ? min(cy + 1, C.ch - 1) : max(cy - 1, 0);
+        const ChromaRow a = chroma_row(cp + (int64_t)cy * cs, 2 * q, C.cw);
+        const ChromaRow b = chroma_row(cp + (int64_t)ny * cs, 2 * q, C.cw);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          dst[i] = jpegm::fancy_h2v2(a.v[quad_c(i)], a.v[quad_n(i)], b.v[quad_c(i)], b.v[quad_n(i)], i & 1);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) jpegm::ycc_to_rgb((int)((yw >> (8 * i)) & 0xFF), cb[i], cr[i], px + 3 * i);
+  }
+}
+
+// One image in its stored orientation, as jpeg_color_kernel reconstructs it: the oriented kernel's path for the
+// untagged images of a mixed batch.
+__device__ __forceinline__ void color_plain(const JpegDesc& d, uint8_t* __restrict__ pool) {
+  const int W = d.width, H = d.height, layout = d.layout;
+  const int qpr = (W + 3) >> 2;  // quads per row
+  const int total = qpr * H;
+  const uint8_t* yp = pool + d.comp[0].plane_off;
+  const int ys = d.comp[0].bw * 8;
+  uint8_t* out_img = pool + d.rgb_off;
+  for (int t = (int)blockIdx.x * 256 + (int)threadIdx.x; t < total; t += (int)gridDim.x * 256) {
+    const int y = t / qpr, q = t - y * qpr;
+    const int x0 = 4 * q;
+    const int n = min(4, W - x0);
+    uint8_t px[12];
+    color_quad(d, pool, yp, ys, layout, y, q, px);
+    uint8_t* out = out_img + ((int64_t)y * W + x0) * 3;
+    if (n == 4 && (W & 3) == 0) {
+      uint32_t w[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        w[k] = (uint32_t)px[4 * k] | ((uint32_t)px[4 * k + 1] << 8) | ((uint32_t)px[4 * k + 2] << 16) |
+               ((uint32_t)px[4 * k + 3] << 24);
+      uint32_t* o32 = reinterpret_cast<uint32_t*>(out);
+      o32[0] = w[0];
+      o32[1] = w[1];
+      o32[2] = w[2];
+    } else {
+      for (int k = 0; k < 3 * n; ++k) out[k] = px[k];
+    }
+  }
+}
+
+// ---- EXIF-oriented output ----------------------------------------------------------------------------------------
+//
+// Source pixel (y, x) of a W x H image goes to (row, column) of the output:
+//   2 (y, W-1-x)   3 (H-1-y, W-1-x)   4 (H-1-y, x)                        output W x H
+//   5 (x, y)       6 (x, H-1-y)       7 (W-1-x, H-1-y)   8 (W-1-x, y)     output H wide, W high
+// A quad is four pixels packed one per dword (r | g << 8 | b << 16) in source order; store_quad writes the first
+// n of them at `out`, last pixel first when `rev` (a mirrored axis), as the plain kernel's 12-byte aligned dword
+// triple when `aligned` (n == 4 and the output width a multiple of 4, so a quad's first column is too, mirrored
+// or not) and as bytes otherwise.
+__device__ __forceinline__ uint32_t pick4(const uint32_t* p, int i) {
+  return i == 0 ? p[0] : i == 1 ? p[1] : i == 2 ? p[2] : p[3];
+}
+
+__device__ __forceinline__ void store_quad(uint8_t* __restrict__ out, const uint32_t* p, int n, bool rev,
+                                           bool aligned) {
+  if (aligned) {
+    const uint32_t a = rev ? p[3] : p[0], b = rev ? p[2] : p[1], c = rev ? p[1] : p[2], e = rev ? p[0] : p[3];
+    uint32_t* o32 = reinterpret_cast<uint32_t*>(out);
+    o32[0] = a | (b << 24);
+    o32[1] = (b >> 8) | (c << 16);
+    o32[2] = (c >> 16) | (e << 8);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (j < n) {
+        const uint32_t v = pick4(p, rev ? n - 1 - j : j);
+        out[3 * j] = (uint8_t)v;
+        out[3 * j + 1] = (uint8_t)(v >> 8);
+        out[3 * j + 2] = (uint8_t)(v >> 16);
+      }
+    }
+  }
+}
+
+// Orientations 5-8 turn a source row into an output column, so a source tile of kTile x kTile pixels is staged in
+// LDS and stored transposed.  kTile = 64: a 256-lane workgroup computes the tile's 16 x 64 quads in 4 steps and
+// then stores its 64 output rows x 16 quads in 4 steps; per step a wave covers 4 output rows with 16 adjacent
+// lanes each, i.e. four contiguous 192-byte segments (one 12-byte store per lane).
+//
+// LDS: one dword per pixel, row pitch kTilePitch = 65 dwords.  Both accesses are ds_*_b32, which CDNA4's LDS
+// serves in two groups of 32 lanes over 32 banks (bank = (addr / 4) mod 32).  A lane's (a, b) = (its index along
+// the fast axis 0..15, along the slow axis 0..63) is laid out so that each 32-lane group holds a in 8g .. 8g + 7
+// and four consecutive b:
+//   write of pixel i of quad a in source row b:   dword b * 65 + 4a + i  -> bank (b + 4a + i) mod 32; 4a takes the
+//     8 multiples of 4 and b the 4 residues between them: 32 distinct banks;
+//   read of row 4a + i of source column b:        dword (4a + i) * 65 + b -> bank (4a + i + b) mod 32: the same set.
+// Under the plain model of 64 banks x 4 B over a whole wave the same holds (a in 0..15, four consecutive b: 64
+// distinct values of b + 4a mod 64), because the pitch is 1 mod 64 as well; 65 is the smallest such pitch that
+// holds a 64-pixel row.  16.25 KB per workgroup.
+constexpr int kTile = 64;
+constexpr int kTilePitch = kTile + 1;
+
+__global__ __launch_bounds__(256) void jpeg_color_oriented_kernel(const JpegDesc* __restrict__ descs,
+                                                                  uint8_t* __restrict__ pool) {
+  __shared__ uint32_t tile[kTile * kTilePitch];
+  const JpegDesc& d = descs[blockIdx.y];
+  const int orient = d.orientation;  // block-uniform: one image per blockIdx.y
+  if (orient <= 1) {
+    color_plain(d, pool);
+    return;
+  }
+  const int W = d.width, H = d.height, layout = d.layout;
+  const uint8_t* yp = pool + d.comp[0].plane_off;
+  const int ys = d.comp[0].bw * 8;
+  uint8_t* out_img = pool + d.rgb_off;
+  if (orient <= 4) {
+    // rows stay rows: the plain kernel's row-quad stores, on a flipped row and / or from a mirrored column
+    const int qpr = (W + 3) >> 2;
+    const int total = qpr * H;
+    const bool rev = orient != 4, flip = orient != 2;
+    for (int t = (int)blockIdx.x * 256 + (int)threadIdx.x; t < total; t += (int)gridDim.x * 256) {
+      const int y = t / qpr, q = t - y * qpr;
+      const int x0 = 4 * q;
+      const int n = min(4, W - x0);
+      uint8_t px[12];
+      color_quad(d, pool, yp, ys, layout, y, q, px);
+      uint32_t p[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        p[i] = (uint32_t)px[3 * i] | ((uint32_t)px[3 * i + 1] << 8) | ((uint32_t)px[3 * i + 2] << 16);
+      const int row = flip ? H - 1 - y : y, col = rev ? W - x0 - n : x0;
+      store_quad(out_img + ((int64_t)row * W + col) * 3, p, n, rev, n == 4 && (W & 3) == 0);
+    }
+    return;
+  }
+  const int tiles_x = (W + kTile - 1) / kTile, tiles_y = (H + kTile - 1) / kTile;
+  const int wave = (int)threadIdx.x >> 6, l = (int)threadIdx.x & 63;
+  const int a = (l & 7) | ((l >> 5) << 3);  // 0..15, 8 per 32-lane group
+  const int b0 = ((l >> 3) & 3) + 4 * wave;  // + 16 per step
+  const bool rev = orient == 6 || orient == 7;  // output columns run against the source rows
+  const bool mirror = orient == 7 || orient == 8;  // output rows run against the source columns
+  // the trip count is uniform over the workgroup (it depends on blockIdx alone), as the barriers need
+  for (int t = (int)blockIdx.x; t < tiles_x * tiles_y; t += (int)gridDim.x) {
+    const int ty = t / tiles_x, tx = t - ty * tiles_x;
+    const int sy = ty * kTile, sx = tx * kTile;
+#pragma unroll
+    for (int step = 0; step < 4; ++step) {
+      const int b = b0 + 16 * step;  // source row within the tile, quad a of it
+      const int y = sy + b, x0 = sx + 4 * a;
+      if (y < H && x0 < W) {
+        uint8_t px[12];
+        color_quad(d, pool, yp, ys, layout, y, x0 >> 2, px);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          tile[b * kTilePitch + 4 * a + i] =
+              (uint32_t)px[3 * i] | ((uint32_t)px[3 * i + 1] << 8) | ((uint32_t)px[3 * i + 2] << 16);
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int step = 0; step < 4; ++step) {
+      const int b = b0 + 16 * step;  // source column within the tile, rows 4a .. 4a + 3 of it
+      const int x = sx + b, y0 = sy + 4 * a;
+      if (x < W && y0 < H) {
+        const int n = min(4, H - y0);
+        uint32_t p[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) p[i] = tile[(4 * a + i) * kTilePitch + b];  // rows >= n: stale, never stored
+        const int row = mirror ? W - 1 - x : x, col = rev ? H - y0 - n : y0;
+        store_quad(out_img + ((int64_t)row * H + col) * 3, p, n, rev, n == 4 && (H & 3) == 0);
+      }
+    }
+    __syncthreads();
+  }
+}
+
 }  // namespace
 
 void jpeg_reconstruct(const JpegDesc* d_descs, uint8_t* d_pool, int n_images, int max_blocks, int64_t max_pixels,
-                      hipStream_t s) {
+                      hipStream_t s, bool oriented) {
   if (n_images <= 0) return;
   const dim3 g1((unsigned)((max_blocks + kBlocksPerGroup - 1) / kBlocksPerGroup), (unsigned)n_images);
   if (max_blocks > 0) hipLaunchKernelGGL(jpeg_idct_kernel, g1, dim3(256), 0, s, d_descs, d_pool);
   // one lane per 4-pixel quad of a row, grid-stride over the image's rows x quads
   const dim3 g2((unsigned)std::max<int64_t>(1, (max_pixels + 1023) / 1024), (unsigned)n_images);
-  if (max_pixels > 0) hipLaunchKernelGGL(jpeg_color_kernel, g2, dim3(256), 0, s, d_descs, d_pool);
+  if (max_pixels <= 0) return;
+  if (oriented) hipLaunchKernelGGL(jpeg_color_oriented_kernel, g2, dim3(256), 0, s, d_descs, d_pool);
+  else hipLaunchKernelGGL(jpeg_color_kernel, g2, dim3(256), 0, s, d_descs, d_pool);
 }
 
 }  // namespace arena

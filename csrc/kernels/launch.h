@@ -480,9 +480,10 @@ void stamp(void* dst, hipStream_t s);
 // Device half of the split JPEG decoder (csrc/kernels/jpeg_idct.hip): for n_images descriptors (jpeg_desc.h)
 // reconstruct packed RGB at d_pool + desc.rgb_off from the quantized coefficient blocks at d_pool +
 // comp.coef_off (sample planes at d_pool + comp.plane_off as scratch).  max_blocks / max_pixels: the largest
-// total_blocks / width * height over the batch (grid sizes).
+// total_blocks / width * height over the batch (grid sizes).  `oriented`: some descriptor has an EXIF
+// orientation other than 1, so the colour stage runs as the oriented kernel; false launches the plain kernels.
 struct JpegDesc;
 void jpeg_reconstruct(const JpegDesc* d_descs, uint8_t* d_pool, int n_images, int max_blocks, int64_t max_pixels,
-                      hipStream_t s);
+                      hipStream_t s, bool oriented = false);
 
 }  // namespace arena

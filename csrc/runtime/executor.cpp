@@ -1177,6 +1177,7 @@ int Executor::submit(const std::vector<InputImage>& imgs) {
   size_t packed_end = off;
   int nj = 0, max_blocks = 0;
   int64_t max_pix = 0;
+  bool oriented = false;  // some JPEG of the batch carries an EXIF orientation: the oriented colour kernel runs
   // packed coefficients sit contiguously right after the host-packed inputs, inside the one staging DMA
   std::vector<size_t> coef_at(n, 0);
   {
@@ -1195,7 +1196,7 @@ int Executor::submit(const std::vector<InputImage>& imgs) {
     const InputImage& im = imgs[i];
     if (im.jpeg == nullptr) continue;
     const JpegInfo& ji = *im.jpeg;
-    if (ji.width != im.w || ji.height != im.h) throw std::runtime_error("submit: JPEG geometry mismatch");
+    if (ji.out_width != im.w || ji.out_height != im.h) throw std::runtime_error("submit: JPEG geometry mismatch");
     const size_t rgb = off, coef = coef_at[i];
     const size_t planes =
         align_up(rgb + (size_t)im.h * im.w * 3, 256);
@@ -1205,6 +1206,7 @@ int Executor::submit(const std::vector<InputImage>& imgs) {
     jdesc[nj] = jpeg_device_desc(ji, (int64_t)coef, (int64_t)planes, (int64_t)rgb);
     max_blocks = std::max(max_blocks, jdesc[nj].total_blocks);
     max_pix = std::max(max_pix, (int64_t)im.h * im.w);
+    oriented |= ji.orientation > 1;
     ++nj;
     off = end;
   }
@@ -1233,7 +1235,7 @@ int Executor::submit(const std::vector<InputImage>& imgs) {
   if (nj > 0) {
     trace::Range tj("arena.jpeg_reconstruct");
     jpeg_reconstruct((const JpegDesc*)(sl.d_in + jpeg_desc_off()), sl.d_in + in_bytes_meta(), nj, max_blocks, max_pix,
-                     sl.stream);
+                     sl.stream, oriented);
     ARENA_HIP_CHECK(hipGetLastError());
   }
   // frames exported to another buffer on this device (arm B's IPC ring): device to device, in stream order

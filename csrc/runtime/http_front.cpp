@@ -1304,7 +1304,7 @@ void HttpFrontEnd::native_decode(DecodeTask& t) {
   if (st == JpegStatus::Corrupt)
     return fail_request(t.conn, err.find("image too large") != std::string::npos ? 413 : 500, err, t.kind);
   const JpegInfo& ji = up->info;
-  InputImage in{nullptr, ji.height, ji.width};
+  InputImage in{nullptr, ji.out_height, ji.out_width};  // the oriented frame
   // Device reconstruction needs the coefficients, the sample planes and the RGB frame in one batch's staging
   // pool (staged_bytes) and the coefficients in one pooled buffer.  A frame too large for either (about
   // > 15 MP at 4:2:0 with the default pool) is reconstructed on the host instead and staged as RGB, as the PIL
@@ -1347,6 +1347,7 @@ void HttpFrontEnd::native_decode(DecodeTask& t) {
   {
     std::lock_guard<std::mutex> sl(stats_mu_);
     ++stats_.native_decoded;
+    if (ji.orientation > 1) ++stats_.oriented_decoded;
     stats_.cpu_decode_ms += thread_cpu_ms() - c0;
   }
   {

@@ -125,6 +125,7 @@ struct FrontStats {
   int64_t requests = 0, ok = 0, bad_request = 0, too_large = 0, unavailable = 0, errors = 0, not_found = 0;
   int64_t connections = 0, open_connections = 0, detections = 0, timeouts = 0;
   int64_t native_decoded = 0, fallback_decoded = 0;  // uploads decoded by the split decoder / the PIL pool
+  int64_t oriented_decoded = 0;  // of native_decoded: uploads with an EXIF orientation other than 1
   int64_t bodies_recycled = 0, bodies_allocated = 0;  // request bodies served by the body pool / newly grown
   double sum_total_ms = 0, sum_decode_ms = 0, sum_queue_ms = 0, sum_gpu_ms = 0;
   // host CPU time (thread CPU clock) of request stages, summed: HTTP + multipart parse on the I/O threads, the

@@ -297,6 +297,31 @@ __attribute__((always_inline)) inline bool decode_block_compact(BitReader& br, c
   return true;
 }
 
+// EXIF orientation of an APP1 payload (rule in jpeg_decode.h); 0 when the payload is not EXIF at all
+int exif_orientation(const uint8_t* seg, size_t sl) {
+  if (sl < 6 || std::memcmp(seg, "Exif\0\0", 6) != 0) return 0;
+  const uint8_t* t = seg + 6;
+  const uint64_t L = sl - 6;
+  if (L < 8) return 1;
+  const bool le = t[0] == 'I' && t[1] == 'I';
+  if (!le && !(t[0] == 'M' && t[1] == 'M')) return 1;
+  auto u16 = [&](uint64_t o) -> uint32_t { return le ? (uint32_t)(t[o] | (t[o + 1] << 8)) : (uint32_t)((t[o] << 8) | t[o + 1]); };
+  auto u32 = [&](uint64_t o) -> uint64_t { return le ? ((uint64_t)u16(o + 2) << 16) | u16(o) : ((uint64_t)u16(o) << 16) | u16(o + 2); };
+  if (u16(2) != 42) return 1;
+  const uint64_t ifd = u32(4);
+  if (ifd + 2 > L) return 1;
+  const uint64_t count = u16(ifd);
+  if (ifd + 2 + 12 * count > L) return 1;  // 64-bit: neither term can wrap
+  for (uint64_t i = 0; i < count; ++i) {
+    const uint64_t e = ifd + 2 + 12 * i;
+    if (u16(e) != 0x0112) continue;
+    if (u16(e + 2) != 3 || u32(e + 4) != 1) return 1;
+    const uint32_t v = u16(e + 8);
+    return v >= 1 && v <= 8 ? (int)v : 1;
+  }
+  return 1;
+}
+
 }  // namespace
 
 JpegStatus jpeg_parse(const uint8_t* data, size_t n, JpegInfo& info, std::string& err, int64_t max_pixels) {
@@ -307,7 +332,7 @@ JpegStatus jpeg_parse(const uint8_t* data, size_t n, JpegInfo& info, std::string
   }
   uint16_t qtab[4][64];
   bool qpresent[4] = {false, false, false, false};
-  bool saw_sof = false, saw_jfif = false, adobe = false;
+  bool saw_sof = false, saw_jfif = false, adobe = false, saw_exif = false;
   int adobe_transform = -1;
   size_t pos = 2;
   while (true) {
@@ -425,6 +450,14 @@ JpegStatus jpeg_parse(const uint8_t* data, size_t n, JpegInfo& info, std::string
       info.restart_interval = be16(seg);
     } else if (m == 0xE0) {
       if (sl >= 5 && std::memcmp(seg, "JFIF\0", 5) == 0) saw_jfif = true;
+    } else if (m == 0xE1) {
+      if (!saw_exif) {  // the first EXIF segment decides, well-formed or not
+        const int o = exif_orientation(seg, sl);
+        if (o) {
+          saw_exif = true;
+          info.orientation = o;
+        }
+      }
     } else if (m == 0xEE) {
       if (sl >= 12 && std::memcmp(seg, "Adobe", 5) == 0) {
         adobe = true;
@@ -529,6 +562,9 @@ JpegStatus jpeg_parse(const uint8_t* data, size_t n, JpegInfo& info, std::string
   }
   info.coef_count = off;
   info.plane_bytes = planes;
+  const bool swap = info.orientation >= 5;
+  info.out_width = swap ? info.height : info.width;
+  info.out_height = swap ? info.width : info.height;
   return JpegStatus::Ok;
 }
 
@@ -798,9 +834,21 @@ void jpeg_coefs_to_rgb(const JpegInfo& info, const int16_t* coef, uint8_t* rgb) 
   const JpegCompDesc& Y = info.comp[0];
   const uint8_t* yp = planes.data() + Y.plane_off;
   const int ys = Y.bw * 8;
+  const int W = info.width, H = info.height, ori = info.orientation;
   for (int y = 0; y < info.height; ++y) {
     for (int x = 0; x < info.width; ++x) {
-      uint8_t* o = rgb + ((int64_t)y * info.width + x) * 3;
+      int64_t at;  // output pixel index of source (y, x)
+      switch (ori) {
+        case 2: at = (int64_t)y * W + (W - 1 - x); break;
+        case 3: at = (int64_t)(H - 1 - y) * W + (W - 1 - x); break;
+        case 4: at = (int64_t)(H - 1 - y) * W + x; break;
+        case 5: at = (int64_t)x * H + y; break;
+        case 6: at = (int64_t)x * H + (H - 1 - y); break;
+        case 7: at = (int64_t)(W - 1 - x) * H + (H - 1 - y); break;
+        case 8: at = (int64_t)(W - 1 - x) * H + y; break;
+        default: at = (int64_t)y * W + x; break;
+      }
+      uint8_t* o = rgb + at * 3;
       const int yy = yp[(int64_t)y * ys + x];
       if (info.layout == JPEG_GRAY) {
         o[0] = o[1] = o[2] = (uint8_t)yy;
@@ -837,6 +885,7 @@ JpegDesc jpeg_device_desc(const JpegInfo& info, int64_t coef_base, int64_t plane
   d.layout = info.layout;
   d.width = info.width;
   d.height = info.height;
+  d.orientation = info.orientation;
   d.rgb_off = rgb_off;
   int64_t total = 0;
   for (int c = 0; c < info.ncomp; ++c) {

@@ -34,6 +34,10 @@ struct JpegInfo {
   int width = 0, height = 0, ncomp = 0;
   int hmax = 1, vmax = 1, mcux = 0, mcuy = 0;
   int layout = -1;
+  // EXIF orientation (1..8; 1 when absent or not well-formed, see jpeg_parse) and the size of the oriented
+  // output: width and height swapped for 5..8.  width / height stay the stored frame's.
+  int orientation = 1;
+  int out_width = 0, out_height = 0;
   int restart_interval = 0;
   int comp_id[kJpegMaxComp] = {};
   int tq[kJpegMaxComp] = {}, td[kJpegMaxComp] = {}, ta[kJpegMaxComp] = {};
@@ -52,6 +56,12 @@ enum class JpegStatus : int { Ok = 0, Unsupported = 1, Corrupt = 2 };
 
 // Parse the markers up to the (single) scan.  `max_pixels` > 0 rejects larger frames as Corrupt with an
 // "image too large" message (the decode-bomb guard of processing/transforms.py).
+//
+// Orientation, as cv2.imdecode honours it (processing/exif.py is the same rule in Python, for the PIL paths): the
+// first APP1 segment before SOS whose payload starts with "Exif\0\0" decides.  Its TIFF header ("II" or "MM", 42,
+// IFD0 offset) leads to IFD0; the first entry with tag 0x0112 counts when it is one SHORT with a value of 1..8.
+// Everything else is orientation 1: no such segment, another type or count, a value of 0 or 9, an IFD or entry
+// table that leaves the segment, an orientation that only XMP states.  Broken EXIF never changes the status.
 JpegStatus jpeg_parse(const uint8_t* data, size_t n, JpegInfo& info, std::string& err, int64_t max_pixels = 0);
 
 // Entropy-decode the scan: info.coef_count int16 quantized coefficients, natural order, one block after the
@@ -78,7 +88,8 @@ void jpeg_compact_to_dense(const JpegInfo& info, const uint8_t* payload, int16_t
 // the payload as dense blocks: itself when dense, else expanded into `scratch`
 const int16_t* jpeg_dense_coefs(const JpegInfo& info, const uint8_t* payload, std::vector<int16_t>& scratch);
 
-// Host reconstruction with the device kernels' exact arithmetic (kernels/jpeg_math.h): packed HxWx3 RGB.
+// Host reconstruction with the device kernels' exact arithmetic (kernels/jpeg_math.h): packed RGB of
+// out_height x out_width pixels, each source pixel placed by info.orientation (table in kernels/jpeg_idct.hip).
 void jpeg_coefs_to_rgb(const JpegInfo& info, const int16_t* coef, uint8_t* rgb);
 
 // The device descriptor of a parsed image, with byte offsets relative to `coef_base` / `plane_base` / `rgb_off`.

@@ -107,7 +107,7 @@ void JpegIngest::run(Task& t) {
     return;
   }
   const JpegInfo& ji = up->info;
-  InputImage in{nullptr, ji.height, ji.width};
+  InputImage in{nullptr, ji.out_height, ji.out_width};  // the oriented frame
   in.export_dst = t.export_dst;
   if (st == JpegStatus::Ok) {
     // device reconstruction when the frame's coefficients, planes and RGB fit one batch's staging pool and a

@@ -25,6 +25,7 @@ from pathlib import Path
 import numpy as np
 
 from ..config import get_controlled_variable
+from .exif import jpeg_orientation, orient
 
 LETTERBOX_COLOR = (114, 114, 114)
 
@@ -60,12 +61,14 @@ def _decode(data: bytes | Path | str, what: str) -> np.ndarray:
     from PIL import Image, UnidentifiedImageError
 
     try:
-        src = io.BytesIO(data) if isinstance(data, (bytes, bytearray, memoryview)) else str(data)
-        with Image.open(src) as im:
+        if not isinstance(data, (bytes, bytearray, memoryview)):
+            data = Path(data).read_bytes()
+        with Image.open(io.BytesIO(data)) as im:
             _check_size(im, what)
             if im.mode != "RGB":  # convert() of an RGB image is a full copy
                 im = im.convert("RGB")
-            arr = np.asarray(im, dtype=np.uint8)
+            # upright, as cv2.imdecode / cv2.imread return a JPEG with an EXIF orientation (exif.py)
+            arr = np.asarray(orient(im, jpeg_orientation(data)), dtype=np.uint8)
     except ImageTooLargeError:
         raise
     except Image.DecompressionBombError as e:
@@ -87,6 +90,7 @@ def decode_rgb(data: bytes | memoryview) -> tuple[int, int, bytes]:
             _check_size(im, "Failed to decode image")
             if im.mode != "RGB":
                 im = im.convert("RGB")
+            im = orient(im, jpeg_orientation(data))
             w, h = im.size
             return h, w, im.tobytes()
     except ImageTooLargeError:

@@ -35,12 +35,14 @@ log = logging.getLogger("arena.server")
 
 
 def probe_size(data: bytes) -> tuple[int, int]:
-    """(height, width) of an encoded upload from its header alone (PIL's lazy open, no pixel decode); the
+    """(height, width) of an encoded upload from its header alone (PIL's lazy open, no pixel decode), as
+    the decode returns it: swapped for a JPEG whose EXIF orientation is 5..8 (processing/exif.py); the
     errors of a failed decode: ValueError, TooLarge beyond ``max_image_pixels``."""
     import io
 
     from PIL import Image, UnidentifiedImageError
 
+    from ..processing.exif import jpeg_orientation
     from ..processing.transforms import max_image_pixels
     from .batching import TooLarge
 
@@ -53,7 +55,7 @@ def probe_size(data: bytes) -> tuple[int, int]:
         raise ValueError(f"Failed to decode image: {e}") from e
     if w * h > max_image_pixels():
         raise TooLarge(f"Failed to decode image: image too large ({w}x{h} pixels > {max_image_pixels()})")
-    return h, w
+    return (w, h) if jpeg_orientation(data) >= 5 else (h, w)
 
 
 class DecodePool:
