@@ -238,6 +238,38 @@ void py_decode(const py::dict& d) {
   detect_decode(p, stream_of(d));
 }
 
+void py_yolo_raw(const py::dict& d) {
+  YoloRawParams p{};
+  auto heads = req<std::vector<uintptr_t>>(d, "head");
+  auto hw = req<std::vector<int>>(d, "hw");
+  auto xs = req<std::vector<int>>(d, "xs");
+  auto st = req<std::vector<float>>(d, "strides");
+  for (int l = 0; l < 3; ++l) {
+    p.head[l] = (const void*)heads.at(l);
+    p.hw[l] = hw.at(l);
+    p.xs[l] = xs.at(l);
+    p.stride[l] = st.at(l);
+  }
+  p.B = req<int>(d, "B");
+  p.out = ptr<void*>(d, "out");
+  p.out_stride = req<size_t>(d, "out_stride");  // bytes
+  p.ctrl = ptr<const Ctrl*>(d, "ctrl");
+  p.f32 = get<int>(d, "f32", 0);
+  yolo_raw(p, stream_of(d));
+}
+
+void py_tensor_in(const py::dict& d) {
+  TensorInParams p{};
+  p.pool = ptr<const uint8_t*>(d, "pool");
+  p.meta = ptr<const ImageMeta*>(d, "meta");
+  p.ctrl = ptr<const Ctrl*>(d, "ctrl");
+  p.out = ptr<void*>(d, "out");
+  p.B = req<int>(d, "B");
+  p.S = req<int>(d, "S");
+  p.f32 = get<int>(d, "f32", 0);
+  tensor_in_s2d(p, stream_of(d));
+}
+
 void py_nms(const py::dict& d) {
   prepare_kernels();
   NmsParams p{};
@@ -585,6 +617,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("set_ir_crop_split", &set_ir_crop_split);
   m.def("letterbox_s2d", &py_letterbox);
   m.def("detect_decode", &py_decode);
+  m.def("yolo_raw", &py_yolo_raw);
+  m.def("tensor_in_s2d", &py_tensor_in);
   m.def("nms", &py_nms);
   m.def("crop_plan", &py_crop_plan);
   m.def("crop_gather_s2d", &py_crop_gather);

@@ -263,7 +263,9 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsParams p) {
   }
 
   const ImageMeta m = p.meta[b];
-  const float inv = 1.0f / m.scale;
+  // divided, as scale_boxes does: x * (1 / scale) is an ulp off for most scales, which crop_plan's (int)
+  // truncation turns into a different pixel rectangle
+  const float scale = m.scale;
   int kept = 0;
   for (int i = 0; i < n; ++i) {
     if (removed[i]) continue;  // block-uniform: written before the last barrier
@@ -272,10 +274,10 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsParams p) {
     const Candidate bi = cand[ki & 0x3FFF];
     if (tid == 0 && kept < p.max_det) {
       Detection d;
-      d.x1 = fminf(fmaxf((bi.x1 - (float)m.pad_w) * inv, 0.f), (float)m.w);
-      d.y1 = fminf(fmaxf((bi.y1 - (float)m.pad_h) * inv, 0.f), (float)m.h);
-      d.x2 = fminf(fmaxf((bi.x2 - (float)m.pad_w) * inv, 0.f), (float)m.w);
-      d.y2 = fminf(fmaxf((bi.y2 - (float)m.pad_h) * inv, 0.f), (float)m.h);
+      d.x1 = fminf(fmaxf((bi.x1 - (float)m.pad_w) / scale, 0.f), (float)m.w);
+      d.y1 = fminf(fmaxf((bi.y1 - (float)m.pad_h) / scale, 0.f), (float)m.h);
+      d.x2 = fminf(fmaxf((bi.x2 - (float)m.pad_w) / scale, 0.f), (float)m.w);
+      d.y2 = fminf(fmaxf((bi.y2 - (float)m.pad_h) / scale, 0.f), (float)m.h);
       d.conf = bi.score;
       d.cls = bi.cls;
       d.pad_[0] = d.pad_[1] = 0.f;
