@@ -1187,6 +1187,10 @@ static bool x3_h16(const ConvParams& p, hipStream_t s) {
 // impl kF32X3Halo: 3x3 stride-1 convs with Kpad == 9 * Cin (tap-major K) and Cin % 4 == 0.  nf > 0 forces the
 // channel tile (impl kF32X3HaloN3 / N2: BN 48 / 32): the 80-channel detect-head convs at NF = 5 need 89 KB of
 // LDS (one workgroup, one wave per SIMD); two 48-channel tiles fit twice per CU at 17 % padded channels.
+// The 144-channel Detect-head pairs ran here as three 48-channel tiles, each staging and splitting the same halo;
+// the headline program now runs them, and its other convs that used this kernel, on x3hp (halo_x3p.hip): the same
+// arithmetic over the pre-split weight planes, all nine fragments in one workgroup (per-tap weight stages).  This
+// kernel stays for the table entries and programs that still name impl 101 / 102 / 103 / 108 / 109.
 static bool x3_halo(const ConvParams& p, hipStream_t s, int nf = 0, int th = 8) {
   if (p.KH != 3 || p.KW != 3 || p.stride != 1 || p.Kpad != 9 * p.Cin || p.Cin % 4 != 0) return false;
   const int ncf = p.Cout_pad / 16;
@@ -1619,6 +1623,11 @@ void conv2d_f32(const ConvParams& p, hipStream_t s) {
     if (p.impl >= kF32X3HR && p.impl < kF32X3HR + kF32X3HRVariants) {
       if (!conv_x3hr(p, s, p.impl - kF32X3HR))
         throw std::runtime_error("conv2d_f32: not an x3hr-eligible conv (3x3 s1 with pre-split weights)");
+      return;
+    }
+    if (p.impl >= kF32X3HP && p.impl < kF32X3HP + kF32X3HPVariants) {
+      if (!conv_x3hp(p, s, p.impl - kF32X3HP))
+        throw std::runtime_error("conv2d_f32: not an x3hp-eligible conv (3x3 s1 with pre-split weights)");
       return;
     }
     if (p.impl == kF32X3H16) {

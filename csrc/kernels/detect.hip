@@ -313,6 +313,7 @@ void prepare_kernels() {
   x3g_prepare();
   c3_x3_prepare();
   x3hg_prepare();
+  x3hp_prepare();
   stem_s2_f32_prepare();
   ARENA_HIP_CHECK(hipFuncSetAttribute((const void*)sppf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                       160 * 1024));

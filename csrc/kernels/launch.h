@@ -122,6 +122,13 @@ constexpr int kF32X3HR = 151;
 constexpr int kF32X3HRVariants = 10;
 constexpr int kF32X3HRPw = 161;
 constexpr int kF32X3HRPwVariants = 6;
+// x3hp: the 16x16x32 halo tiles of kF32X3Halo* over the pre-split weights (halo_x3p.hip), variant v; bit-identical
+// to impl 101 / 102 / 103 / 108 / 109 on every conv they take
+constexpr int kF32X3HP = 191;
+constexpr int kF32X3HPVariants = 9;
+bool x3hp_supported(const ConvParams& p);
+bool conv_x3hp(const ConvParams& p, hipStream_t s, int v);  // false if the conv or variant is not supported
+void x3hp_prepare();
 bool conv_x3hr(const ConvParams& p, hipStream_t s, int v);
 bool conv_x3hr_pw(const ConvParams& p, hipStream_t s, int v);
 bool conv_fc_f32(const ConvParams& p, hipStream_t s);

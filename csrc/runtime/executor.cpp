@@ -353,6 +353,7 @@ void Executor::add_bucket(int B, const int64_t* offsets, int n_buffers, int64_t 
                                 (v >= kF32X3HGPwSmall && v < kF32X3HGPwSmall + kF32X3HGPwSmallVariants) ||
                                 (v >= kF32X3HR && v < kF32X3HR + kF32X3HRVariants) ||
                                 (v >= kF32X3HRPw && v < kF32X3HRPw + kF32X3HRPwVariants) ||
+                                (v >= kF32X3HP && v < kF32X3HP + kF32X3HPVariants) ||
                                 (v >= kF32X3GSK && v < kF32X3GSK + kF32X3GSKVariants)
                           : v >= 0 && v <= 3;
       if (!ok || (v != 0 && prog_[i][0] != OP_CONV)) throw std::runtime_error("add_bucket: bad tuning entry");
@@ -413,6 +414,9 @@ void Executor::autotune(Bucket& bk) {
                                        kF32X3HR + 5, kF32X3HR + 6, kF32X3HR + 7, kF32X3HR + 8, kF32X3HR + 9,
                                        kF32X3HRPw + 0, kF32X3HRPw + 1, kF32X3HRPw + 2, kF32X3HRPw + 3,
                                        kF32X3HRPw + 4, kF32X3HRPw + 5,
+                                       // x3hp: the 16-wide halo tiles over pre-split weights (halo_x3p.hip)
+                                       kF32X3HP + 0, kF32X3HP + 1, kF32X3HP + 2, kF32X3HP + 3, kF32X3HP + 4,
+                                       kF32X3HP + 5, kF32X3HP + 6, kF32X3HP + 7, kF32X3HP + 8,
                                        // split-K x3g (small grids: bucket 1 / 2); skipped where the workspace
                                        // is too small
                                        kF32X3GSK + 0, kF32X3GSK + 1, kF32X3GSK + 2, kF32X3GSK + 3, kF32X3GSK + 4,

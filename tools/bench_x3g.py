@@ -49,11 +49,13 @@ def main(argv=None) -> int:
     ap.add_argument("--impls", default="111,112,113,114,115,116")
     ap.add_argument("--shapes", default=",".join(SHAPES))
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--batch", type=int, default=0, help="batch size instead of the shape's own (bucket capacity)")
     a = ap.parse_args(argv)
     dev = torch.device("cuda", 0)
     g = torch.Generator().manual_seed(0)
     for name in a.shapes.split(","):
         B, H, Cin, Cout, k, s = SHAPES[name]
+        B = a.batch or B
         x = (torch.rand(B, H, H, Cin, generator=g) * 2 - 0.5).to(dev)
         w = torch.randn(Cout, Cin, k, k, generator=g) / (Cin * k * k) ** 0.5
         b = torch.randn(Cout, generator=g) * 0.1
