@@ -1,13 +1,17 @@
 // pybind11 bindings of the split JPEG decoder (runtime/jpeg_decode.h, kernels/jpeg_idct.hip): the host
 // entropy decoder and reference reconstruction for tests / host-only decoding, and a stand-alone device
 // reconstruction of a list of uploads (the kernel-vs-reference tests; the serving path runs the same kernels
-// inside Executor::submit).
+// inside Executor::submit) — and of the split JPEG crop encoder (runtime/jpeg_encode.h, kernels/jpeg_fdct.hip): the
+// host encoder and reference arithmetic, a stand-alone device encode of the crops of one frame, and the
+// CropJpegEncoder the detection service drives.
 #include <hip/hip_runtime.h>
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
 #include <cstring>
+#include <future>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -15,6 +19,7 @@
 #include "kernels/jpeg_desc.h"
 #include "kernels/launch.h"
 #include "runtime/jpeg_decode.h"
+#include "runtime/jpeg_encode.h"
 
 namespace py = pybind11;
 
@@ -74,6 +79,91 @@ void check(hipError_t e, const char* what) {
 }
 
 int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
+
+// ---- crop encoder ---------------------------------------------------------------------------------------------
+
+using U8Array = py::array_t<uint8_t, py::array::c_style | py::array::forcecast>;
+
+void check_rgb(const U8Array& a, const char* what) {
+  if (a.ndim() != 3 || a.shape(2) != 3 || a.shape(0) < 1 || a.shape(1) < 1)
+    throw std::invalid_argument(std::string(what) + " must be HxWx3 uint8 with H, W >= 1");
+  if (a.shape(0) > 65535 || a.shape(1) > 65535) throw std::invalid_argument(std::string(what) + " is too large for a JPEG");
+}
+
+py::bytes to_bytes(const std::vector<uint8_t>& v) { return py::bytes((const char*)v.data(), v.size()); }
+
+// rows of at least four numbers (x1, y1, x2, y2, ...): a list of sequences or an N x >=4 array
+std::vector<CropBox> to_boxes(const py::object& boxes) {
+  std::vector<CropBox> out;
+  for (py::handle h : boxes) {
+    py::sequence r = py::reinterpret_borrow<py::sequence>(h);
+    if (py::len(r) < 4) throw std::invalid_argument("a box needs x1, y1, x2, y2");
+    out.push_back({r[0].cast<double>(), r[1].cast<double>(), r[2].cast<double>(), r[3].cast<double>()});
+  }
+  return out;
+}
+
+constexpr uint8_t kZigzagToNatural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,
+                                          12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
+                                          35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
+                                          58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// Upload `frame`, encode `boxes` with a CropJpegEncoder of its own, check the guards around its device buffer.
+py::dict encode_device(const U8Array& frame, const py::object& boxes, int device, int64_t capacity_bytes,
+                       bool want_coefs) {
+  check_rgb(frame, "frame");
+  const int h = (int)frame.shape(0), w = (int)frame.shape(1);
+  std::vector<CropBox> bx = to_boxes(boxes);
+  const size_t bytes = (size_t)h * w * 3;
+  CropJpegEncoder::Blobs blobs;
+  std::vector<std::vector<int16_t>> coefs;
+  std::string err;
+  int64_t launches = 0;
+  {
+    py::gil_scoped_release nogil;
+    check(hipSetDevice(device), "hipSetDevice");
+    uint8_t* d_frame = nullptr;
+    check(hipMalloc((void**)&d_frame, bytes), "hipMalloc frame");
+    try {
+      check(hipMemcpy(d_frame, frame.data(), bytes, hipMemcpyHostToDevice), "H2D frame");
+      CropJpegEncoder enc(device, capacity_bytes, 2);
+      enc.keep_coefs = want_coefs;
+      std::promise<void> p;
+      enc.submit(d_frame, h, w, std::move(bx), [&](CropJpegEncoder::Blobs&& b, std::string&& e) {
+        blobs = std::move(b);
+        err = std::move(e);
+        p.set_value();
+      }, (int64_t)bytes);
+      p.get_future().wait();
+      enc.stop();
+      if (err.empty()) err = enc.check_guards();
+      coefs = std::move(enc.last_coefs);
+      launches = enc.launches();
+    } catch (...) {
+      (void)hipFree(d_frame);
+      throw;
+    }
+    (void)hipFree(d_frame);
+  }
+  if (!err.empty()) throw std::runtime_error("jpeg_encode_device: " + err);
+  py::dict out;
+  py::list bl;
+  for (const auto& b : blobs) bl.append(to_bytes(b));
+  out["blobs"] = bl;
+  out["launches"] = launches;
+  if (want_coefs) {
+    py::list cl;
+    for (const auto& c : coefs) {  // device layout: natural order; handed out in zigzag order like the host oracle
+      py::array_t<int16_t> a({(py::ssize_t)(c.size() / 64), (py::ssize_t)64});
+      int16_t* dst = a.mutable_data();
+      for (size_t b = 0; b < c.size() / 64; ++b)
+        for (int z = 0; z < 64; ++z) dst[b * 64 + z] = c[b * 64 + kZigzagToNatural[z]];
+      cl.append(a);
+    }
+    out["coefs"] = cl;
+  }
+  return out;
+}
 
 }  // namespace
 
@@ -206,6 +296,123 @@ void bind_jpeg(py::module& m) {
       py::arg("uploads"), py::arg("device") = 0, py::arg("guard") = false,
       "Entropy-decode on the host, reconstruct on the GPU (jpeg_idct.hip): list of HxWx3 uint8 in the EXIF\n"
       "orientation.  guard=True surrounds each RGB region with guard bytes and raises if the kernels touched them.");
+  // ---- crop encoder ----
+  m.attr("SIZEOF_JPEG_ENC_DESC") = (int)sizeof(JpegEncDesc);
+
+  m.def(
+      "jpeg_enc_tables",
+      [](int quality, bool zigzag) {
+        const JpegEncTables t = jpeg_enc_tables(quality);
+        py::array_t<uint16_t> a({(py::ssize_t)2, (py::ssize_t)64});
+        for (int c = 0; c < 2; ++c)
+          for (int k = 0; k < 64; ++k) a.mutable_at(c, k) = t.q[c][zigzag ? kZigzagToNatural[k] : k];
+        return a;
+      },
+      py::arg("quality") = kCropJpegQuality, py::arg("zigzag") = false,
+      "Annex K luminance / chrominance tables under IJG quality scaling: uint16[2][64], natural order (zigzag=True:\n"
+      "the order of a DQT segment).");
+
+  m.def(
+      "jpeg_encode_coefs_host",
+      [](U8Array crop, bool zigzag) {
+        check_rgb(crop, "crop");
+        const int h = (int)crop.shape(0), w = (int)crop.shape(1);
+        py::array_t<int16_t> a({(py::ssize_t)jpeg_enc_blocks(w, h), (py::ssize_t)64});
+        jpeg_encode_coefs_host<int32_t>(crop.data(), (int64_t)w * 3, w, h, jpeg_enc_tables(kCropJpegQuality),
+                                        a.mutable_data(), zigzag);
+        return a;
+      },
+      py::arg("crop"), py::arg("zigzag") = true,
+      "Host oracle of the encoder kernel: int16[blocks][64] quantised coefficients of a 4:2:0 quality-95 JPEG, blocks\n"
+      "in scan order MCU by MCU (Y00 Y01 Y10 Y11 Cb Cr), each in zigzag (default) or natural order.  Dummy slots of\n"
+      "partial MCUs hold the transform of edge-clamped pixels; jpeg_write replaces them.");
+
+  m.def(
+      "jpeg_write",
+      [](int w, int h, py::array_t<int16_t, py::array::c_style | py::array::forcecast> coefs, bool natural) {
+        if (w < 1 || h < 1 || w > 65535 || h > 65535) throw std::invalid_argument("bad size");
+        if (coefs.size() != jpeg_enc_blocks(w, h) * 64) throw std::invalid_argument("coefficient count does not match the size");
+        return to_bytes(jpeg_write(w, h, coefs.data(), jpeg_enc_tables(kCropJpegQuality), natural));
+      },
+      py::arg("w"), py::arg("h"), py::arg("coefs"), py::arg("natural") = false,
+      "Markers + Huffman scan of a w x h crop from its coefficient blocks (layout of jpeg_encode_coefs_host).");
+
+  m.def(
+      "jpeg_encode_host",
+      [](U8Array crop) {
+        check_rgb(crop, "crop");
+        const int h = (int)crop.shape(0), w = (int)crop.shape(1);
+        std::vector<uint8_t> out;
+        {
+          py::gil_scoped_release nogil;
+          out = jpeg_encode_host(crop.data(), (int64_t)w * 3, w, h, jpeg_enc_tables(kCropJpegQuality));
+        }
+        return to_bytes(out);
+      },
+      py::arg("crop"), "Whole encode on the host: the bytes of PIL's quality-95 JPEG of an HxWx3 uint8 crop.");
+
+  m.def(
+      "jpeg_encode_device",
+      [](U8Array frame, py::object boxes, int device, int64_t capacity_bytes) {
+        return encode_device(frame, boxes, device, capacity_bytes, false)["blobs"];
+      },
+      py::arg("frame"), py::arg("boxes"), py::arg("device") = 0, py::arg("capacity_bytes") = 0,
+      "Upload an HxWx3 uint8 frame and encode the crops of `boxes` (x1, y1, x2, y2 floats, clipped like\n"
+      "crop_bounds) on the GPU: list of bytes.  The encoder's device buffer (capacity_bytes, 0 = default) lies\n"
+      "between guard bytes; raises if the kernel touched them.");
+  m.def(
+      "jpeg_encode_device_coefs",
+      [](U8Array frame, py::object boxes, int device, int64_t capacity_bytes) {
+        return encode_device(frame, boxes, device, capacity_bytes, true);
+      },
+      py::arg("frame"), py::arg("boxes"), py::arg("device") = 0, py::arg("capacity_bytes") = 0,
+      "jpeg_encode_device that also returns what the kernel wrote: dict(blobs, coefs = int16[blocks][64] per box in\n"
+      "zigzag order (empty for an empty box), launches).");
+
+  py::class_<CropJpegEncoder>(m, "CropJpegEncoder")
+      .def(py::init([](int device, int64_t capacity_bytes, int threads) {
+             py::gil_scoped_release nogil;
+             return new CropJpegEncoder(device, capacity_bytes, threads);
+           }),
+           py::arg("device") = 0, py::arg("capacity_bytes") = 0, py::arg("threads") = 2)
+      .def(
+          "submit",
+          [](CropJpegEncoder& e, uintptr_t frame_ptr, int frame_h, int frame_w, py::object boxes, py::function done,
+             int64_t frame_bytes) {
+            std::vector<CropBox> bx = to_boxes(boxes);
+            std::shared_ptr<py::function> cb(new py::function(std::move(done)), [](py::function* fn) {
+              py::gil_scoped_acquire gil;
+              delete fn;
+            });
+            py::gil_scoped_release nogil;
+            e.submit((const uint8_t*)frame_ptr, frame_h, frame_w, std::move(bx),
+                     [cb](CropJpegEncoder::Blobs&& blobs, std::string&& err) {
+                       py::gil_scoped_acquire gil;
+                       try {
+                         if (!err.empty()) {
+                           (*cb)(py::none(), err);
+                         } else {
+                           py::list bl;
+                           for (const auto& b : blobs) bl.append(to_bytes(b));
+                           (*cb)(bl, std::string());
+                         }
+                       } catch (py::error_already_set& ex) {
+                         ex.discard_as_unraisable("CropJpegEncoder done");
+                       }
+                     },
+                     frame_bytes);
+          },
+          py::arg("frame_ptr"), py::arg("frame_h"), py::arg("frame_w"), py::arg("boxes"), py::arg("done"),
+          py::arg("frame_bytes") = 0,
+          "Encode the crops of `boxes` from the packed RGB frame at device address frame_ptr (frame_bytes: size of the\n"
+          "buffer there, 0 = the frame's).  done(list of bytes, '') or done(None, error) is called from an encoder\n"
+          "thread; the frame must stay valid until then.")
+      .def_property_readonly("capacity", &CropJpegEncoder::capacity)
+      .def_property_readonly("launches", &CropJpegEncoder::launches)
+      .def("stop", [](CropJpegEncoder& e) {
+        py::gil_scoped_release nogil;
+        e.stop();
+      });
 }
 
 }  // namespace arena

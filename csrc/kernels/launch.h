@@ -493,4 +493,13 @@ struct JpegDesc;
 void jpeg_reconstruct(const JpegDesc* d_descs, uint8_t* d_pool, int n_images, int max_blocks, int64_t max_pixels,
                       hipStream_t s, bool oriented = false);
 
+// Device half of the JPEG crop encoder (csrc/kernels/jpeg_fdct.hip): for n_crops descriptors (jpeg_enc_desc.h)
+// read each crop from the packed RGB frame at d_frame and write its quantised 4:2:0 coefficient blocks (int16,
+// natural order, MCU by MCU) at d_coef + desc.out_off.  d_qt: uint16[2][64] luminance / chrominance tables in
+// natural order.  max_blocks: the largest total_blocks over the descriptors.  The caller has validated that every
+// crop window lies inside the frame and every output range inside the coefficient buffer.
+struct JpegEncDesc;
+void jpeg_forward(const JpegEncDesc* d_descs, const uint8_t* d_frame, uint8_t* d_coef, const uint16_t* d_qt,
+                  int n_crops, int max_blocks, hipStream_t s);
+
 }  // namespace arena

@@ -11,9 +11,16 @@
 
 ``decode_crop`` sniffs the format, so a classification service accepts all
 three from any client.
+
+``GpuCropEncoder`` (``ARENA_CROP_ENCODE=gpu``) makes the ``jpeg`` bytes without
+host pixels: the GPU cuts each crop out of the device-resident frame and does
+everything up to quantisation (csrc/kernels/jpeg_fdct.hip), C++ threads do the
+Huffman pass (csrc/runtime/jpeg_encode.h).  The bytes are those of
+``encode_crop(extract_crop(frame, box), "jpeg")``.
 """
 from __future__ import annotations
 
+import asyncio
 import io
 import struct
 
@@ -55,3 +62,43 @@ def decode_crop(data: bytes) -> np.ndarray:
     elif arr.shape[2] == 4:
         arr = arr[:, :, :3]
     return np.ascontiguousarray(arr, dtype=np.uint8)
+
+
+class GpuCropEncoder:
+    """Async face of the native ``CropJpegEncoder``: ``await encode(frame_ptr, h, w, det)`` gives one JPEG per
+    detection, cut from the packed RGB frame at device address ``frame_ptr``.  The frame must stay untouched until
+    the call has completed; a cancelled caller therefore keeps waiting (the await is shielded) — see
+    ``detection_service`` for how the frame's ring slot is held."""
+
+    def __init__(self, device: int = 0, capacity_bytes: int = 0, threads: int = 2, native_encoder=None):
+        if native_encoder is None:
+            from ..ops import native
+
+            native_encoder = native().CropJpegEncoder(device, capacity_bytes, threads)
+        self.enc = native_encoder
+
+    def submit(self, frame_ptr: int, h: int, w: int, det, frame_bytes: int = 0) -> "asyncio.Future[list[bytes]]":
+        """Start the encode; the future completes on the running loop with the blobs or a RuntimeError."""
+        loop = asyncio.get_running_loop()
+        fut: asyncio.Future = loop.create_future()
+
+        def finish(blobs, error):
+            if fut.done():
+                return
+            if error:
+                fut.set_exception(RuntimeError(error))
+            else:
+                fut.set_result(list(blobs))
+
+        def done(blobs, error):  # on an encoder thread
+            loop.call_soon_threadsafe(finish, blobs, error)
+
+        boxes = [(float(d[0]), float(d[1]), float(d[2]), float(d[3])) for d in det]
+        self.enc.submit(int(frame_ptr), int(h), int(w), boxes, done, int(frame_bytes))
+        return fut
+
+    async def encode(self, frame_ptr: int, h: int, w: int, det, frame_bytes: int = 0) -> list[bytes]:
+        return await asyncio.shield(self.submit(frame_ptr, h, w, det, frame_bytes))
+
+    def close(self) -> None:
+        self.enc.stop()

@@ -12,7 +12,9 @@ Additions: ``transport`` selects jpeg (reference) / png / raw crops,
 ``classify_device`` sends one ``ClassifyBatch`` that names a device-resident
 frame instead of carrying crops (``transport="device"``,
 server/device_transport.py; crops of frames that do not fit the ring still
-go as JPEG).
+go as JPEG).  The ``*_encoded`` methods send crops that are already encoded
+(``ARENA_CROP_ENCODE=gpu``: server/crop_codec.GpuCropEncoder makes the same
+JPEG bytes without host pixels).
 """
 from __future__ import annotations
 
@@ -53,7 +55,11 @@ class ClassificationClient:
         return self.stub is not None
 
     def _request(self, rid: str, crop: np.ndarray, box: dict | None):
-        req = pb.ClassificationRequest(request_id=rid, image_crop=encode_crop(crop, self.codec))
+        return self._request_encoded(rid, encode_crop(crop, self.codec), box)
+
+    @staticmethod
+    def _request_encoded(rid: str, blob: bytes, box: dict | None):
+        req = pb.ClassificationRequest(request_id=rid, image_crop=blob)
         if box:
             req.source_box.x1 = float(box["x1"])
             req.source_box.y1 = float(box["y1"])
@@ -76,6 +82,22 @@ class ClassificationClient:
     async def classify_batch(self, request_id: str, crops: list[np.ndarray], boxes: list[dict]):
         return await self._batch(pb.BatchClassificationRequest(
             requests=[self._request(f"{request_id}_{i}", c, b) for i, (c, b) in enumerate(zip(crops, boxes))]))
+
+    async def classify_encoded(self, rid: str, blob: bytes, box: dict | None = None):
+        """``classify`` of a crop that is already encoded (server/crop_codec.GpuCropEncoder)."""
+        try:
+            return await self.stub.Classify(self._request_encoded(rid, blob, box), timeout=self.timeout_s)
+        except grpc.aio.AioRpcError as e:
+            return pb.ClassificationResponse(request_id=rid, error=f"{e.code().name}: {e.details()}")
+
+    async def classify_parallel_encoded(self, request_id: str, blobs: list[bytes], boxes: list[dict]):
+        return await asyncio.gather(*(self.classify_encoded(f"{request_id}_{i}", c, b)
+                                      for i, (c, b) in enumerate(zip(blobs, boxes))))
+
+    async def classify_batch_encoded(self, request_id: str, blobs: list[bytes], boxes: list[dict]):
+        return await self._batch(pb.BatchClassificationRequest(
+            requests=[self._request_encoded(f"{request_id}_{i}", c, b)
+                      for i, (c, b) in enumerate(zip(blobs, boxes))]))
 
     async def classify_device(self, request_id: str, ref, boxes: list[dict]):
         """All crops of one frame: ``ref`` (pb.DeviceImageRef) names the frame, ``boxes`` the crops."""
@@ -144,6 +166,18 @@ class ClassificationClientPool:
     async def classify_batch(self, request_id: str, crops: list[np.ndarray], boxes: list[dict]):
         i = self.pick()
         return await self._on(i, self.clients[i].classify_batch(request_id, crops, boxes))
+
+    async def classify_encoded(self, rid: str, blob: bytes, box: dict | None = None):
+        i = self.pick()
+        return await self._on(i, self.clients[i].classify_encoded(rid, blob, box))
+
+    async def classify_parallel_encoded(self, request_id: str, blobs: list[bytes], boxes: list[dict]):
+        return await asyncio.gather(*(self.classify_encoded(f"{request_id}_{i}", c, b)
+                                      for i, (c, b) in enumerate(zip(blobs, boxes))))
+
+    async def classify_batch_encoded(self, request_id: str, blobs: list[bytes], boxes: list[dict]):
+        i = self.pick()
+        return await self._on(i, self.clients[i].classify_batch_encoded(request_id, blobs, boxes))
 
     async def classify_device(self, request_id: str, ref, boxes: list[dict]):
         i = self.pick()

@@ -54,6 +54,7 @@ SOURCES = [
     "kernels/head_pool.hip",
     "kernels/fc_splitk.hip",
     "kernels/jpeg_idct.hip",
+    "kernels/jpeg_fdct.hip",
     "runtime/executor.cpp",
     "runtime/batcher.cpp",
     "runtime/http_front.cpp",
@@ -62,6 +63,8 @@ SOURCES = [
     "runtime/trace.cpp",
     "runtime/jpeg_decode.cpp",
     "runtime/jpeg_ingest.cpp",
+    "runtime/jpeg_encode.cpp",
+    "runtime/jpeg_encode_device.cpp",
     "runtime/kserve.cpp",
     "runtime/crash_trace.cpp",
     "bindings_jpeg.cpp",
