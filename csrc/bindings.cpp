@@ -614,6 +614,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("set_irx_slices_big", &set_irx_slices_big);
   m.def("set_ir_t14", &set_ir_t14);
   m.def("set_ir_crop", &set_ir_crop);
+  m.def("set_ir_s2k16", &set_ir_s2k16);
   m.def("set_ir_crop_split", &set_ir_crop_split);
   m.def("letterbox_s2d", &py_letterbox);
   m.def("detect_decode", &py_decode);

@@ -446,6 +446,7 @@ void ir_block_f32(const IrParams& p, hipStream_t s) {
   if (p.Ho != (p.H + 2 - 3) / p.stride + 1 || p.Wo != (p.W + 2 - 3) / p.stride + 1)
     throw std::runtime_error("ir_block_f32: output size mismatch");
   if (p.B <= 0) return;
+  if (ir_s2k16_x3(p, s)) return;  // stride 2 from 16 channels (block 2): K-packed x3 MFMAs (ir_s2k16_x3.hip)
   bool ok;
   if (p.stride == 1 && irf_tw16(p))
     ok = p.expand ? irf_nto<1, 8, 16, true>(p, s) : irf_nto<1, 8, 16, false>(p, s);

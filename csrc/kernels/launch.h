@@ -201,6 +201,10 @@ bool ir_tile_x3(const IrParams& p, hipStream_t s);
 bool ir_tile_x3_supported(int stride, int inp_pad, int hid_pad, int oup_pad, int expand);
 void ir_tile_x3_prepare();
 bool ir_stem_x3(const IrParams& p, hipStream_t s);  // IrParams.stem with x3w: split-plane stem / project weights
+// Stride-2 block with a 16-channel input on K-packed x3 MFMAs over the fp32 weights of ir_block_f32
+// (csrc/kernels/ir_s2k16_x3.hip); false: not that geometry, or switched off
+bool ir_s2k16_x3(const IrParams& p, hipStream_t s);
+void set_ir_s2k16(bool v);  // ARENA_IR_S2K16=0: that block stays on ir_f32.hip's exact-fp32 MFMAs
 void ir_prepare();
 void set_ir_t14(bool v);  // ARENA_IR_T14=1: stride-1 14x14 blocks use one whole-crop tile
 void set_ir_crop(bool v);

@@ -63,6 +63,9 @@ class Settings(BaseModel):
     ARENA_WEIGHT_SEED: int = 0
     ARENA_FAULT_EVERY: int = 0          # inject a failure every k-th request (0 = off)
     ARENA_INFER_SERVICE: int = 0        # classification gRPC server also serves inference.InferenceService/Infer
+    # kernel switch the native library reads from the process environment when it loads (listed here so that the
+    # .env template's key is a known setting): 1 K-packed x3 kernel for fp32 MobileNetV2 block 2, 0 the exact-fp32 one
+    ARENA_IR_S2K16: int = 1
 
     @classmethod
     def from_env(cls, env_file: str | Path = ".env", **overrides) -> "Settings":

@@ -2,9 +2,10 @@
 """Standalone timing of the fused fp32 inverted-residual kernels (csrc/kernels/ir_crop_f32.hip and
 ir_f32.hip) on MobileNetV2 block shapes, over ``--crops`` crops; ``--dbg`` lists diagnostic phase masks of
 ir_crop_f32 (1 no expand MFMA, 2 no depthwise, 4 no project MFMA, 8 no per-chunk weight fetch, 16 no Wp
-staging store) to locate where a chunk's time goes.
+staging store) to locate where a chunk's time goes; ``--s2k16 0|1`` sets the native switch of the stride-2 16-channel-input
+block (csrc/kernels/ir_s2k16_x3.hip; 0: ir_f32's exact-fp32 kernel), shape (112, 16, 96, 24, 2).
 
-Usage (GPU): python tools/bench_irc.py [--crops 128] [--dbg 0,1,2,4,8,16,31]
+Usage (GPU): python tools/bench_irc.py [--crops 128] [--dbg 0,1,2,4,8,16,31] [--s2k16 0|1]
 """
 from __future__ import annotations
 
@@ -29,6 +30,8 @@ def main(argv=None) -> int:
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--dbg", default="0")
     ap.add_argument("--small", action="store_true", help="also the 14x14 / 7x7 shapes (ir_crop_f32)")
+    ap.add_argument("--s2k16", type=int, choices=[0, 1], default=None,
+                    help="block 2 on the K-packed x3 kernel (1) or on ir_f32 (0); default: the library's setting")
     a = ap.parse_args(argv)
     import torch
 
@@ -37,6 +40,8 @@ def main(argv=None) -> int:
     from inference_arena_amd.ops.functional import _ptr, _stream
 
     C = native()
+    if a.s2k16 is not None:
+        C.set_ir_s2k16(bool(a.s2k16))
     dev = torch.device("cuda", 0)
     g = torch.Generator().manual_seed(0)
     for H, inp, hid, oup, s, res in SHAPES:
@@ -69,6 +74,7 @@ def main(argv=None) -> int:
             t1.record()
             torch.cuda.synchronize()
             print(json.dumps({"H": H, "inp": inp, "hid": hid, "oup": oup, "s": s, "x3": bool(x3), "dbg": dbg,
+                              **({"s2k16": a.s2k16} if a.s2k16 is not None else {}),
                               "us": round(t0.elapsed_time(t1) / a.reps * 1e3, 1)}), flush=True)
     return 0
 
