@@ -90,6 +90,9 @@ void py_conv2d(const py::dict& d) {
   p.pw_cout = get<int>(d, "pw_cout", 0);
   p.pw_kpad = get<int>(d, "pw_kpad", 0);
   p.pw_act = get<int>(d, "pw_act", 0);
+  p.gate = ptr<const float*>(d, "gate");
+  p.gate_n = get<int>(d, "gate_n", 0);
+  p.gate_min = get<float>(d, "gate_min", 0.f);
   p.w3 = ptr<const void*>(d, "w3");
   p.sk_ws = ptr<float*>(d, "sk_ws");
   p.sk_ws_bytes = get<int64_t>(d, "sk_ws_bytes", 0);
@@ -616,6 +619,29 @@ PYBIND11_MODULE(_C, m) {
   m.def("set_ir_crop", &set_ir_crop);
   m.def("set_ir_s2k16", &set_ir_s2k16);
   m.def("set_ir_crop_split", &set_ir_crop_split);
+  // Detect-head tile gate (runtime/head_gate.h)
+  m.def("set_head_gate", &set_head_gate);
+  m.def("get_head_gate", &get_head_gate);
+  m.def(
+      "head_gate_min",
+      [](float conf_thr) -> py::object {
+        float g;
+        if (!head_gate_min(conf_thr, &g)) return py::none();
+        return py::float_(g);
+      },
+      py::arg("conf_thr"), "the gate's logit threshold for a confidence threshold (float32); None: the gate is off");
+  m.def(
+      "head_gate_pairs",
+      [](py::array_t<int64_t, py::array::c_style> ops) {
+        if (ops.ndim() != 2 || ops.shape(1) != kOpFields) throw std::runtime_error("ops must be int64 [n, OP_FIELDS]");
+        py::list out;
+        for (const HeadGatePair& gp : head_gate_pairs(ops.data(), (int)ops.shape(0), kOpFields))
+          out.append(py::make_tuple(gp.box, gp.cls, gp.level));
+        return out;
+      },
+      py::arg("ops"), "[(box conv op, class conv op, level)] of a program's records");
+  m.attr("HEAD_BOX_CHANNELS") = kHeadBoxChannels;
+  m.attr("HEAD_CLS_CHANNELS") = kHeadClsChannels;
   m.def("letterbox_s2d", &py_letterbox);
   m.def("detect_decode", &py_decode);
   m.def("yolo_raw", &py_yolo_raw);
@@ -797,6 +823,9 @@ PYBIND11_MODULE(_C, m) {
              return e.submit_device(imgs, dets);
            })
       .def("conv_choices", &Executor::conv_choices)
+      .def("exec_order", &Executor::exec_order, py::arg("B"),
+           "program op indices in the order bucket B's graphs launch them")
+      .def("gated_ops", &Executor::gated_ops, py::arg("B"), "ops of bucket B that run with a tile gate")
       .def("stream", &Executor::stream);
 
   py::class_<SplitInstance, std::shared_ptr<SplitInstance>>(m, "SplitInstance")

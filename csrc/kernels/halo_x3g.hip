@@ -44,6 +44,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int HG_P = 56;  // bf16 per LDS row: 3 planes x 16 k + 8 pad (112 B)
+constexpr int HG_GATE_MAX_N = 80;  // gating channels per pixel at most (ConvParams.gate_n): the Detect head's classes
 
 __host__ __device__ constexpr int hg_th(int TW, int WM, int TM) { return WM * TM * (32 / TW); }
 __host__ __device__ constexpr int hg_lds_bytes(int TW, int WM, int WN, int TM, int TN) {
@@ -215,6 +216,32 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_x3hg_kernel(const ConvParam
   const int oy0 = ty * TH, ox0 = tx * TW, n0 = nt * BN;
   const int iy0 = oy0 - p.pad_t, ix0 = ox0 - p.pad_l;
   const int H = p.H, W = p.W, Cin = p.Cin;
+
+  // ---- tile gate (ConvParams.gate): nothing reads this tile's output unless one of its pixels holds a gating
+  // logit >= gate_min, so a tile without one is left as it is; before any halo or weight load
+  if constexpr (PWN > 0) {
+    if (p.gate != nullptr) {
+      constexpr int GJ = (TH * TW * (HG_GATE_MAX_N / 4) + NT - 1) / NT;  // float4 items per thread at most
+      const int nq = p.gate_n >> 2;  // host: gate_n % 4 == 0, 0 < gate_n <= HG_GATE_MAX_N
+      const int items = TH * TW * nq;
+      const float gm = p.gate_min;
+      const float nan = __builtin_nanf("");  // an item outside the tile or the map passes nothing
+      float4 gv[GJ];
+#pragma unroll
+      for (int j = 0; j < GJ; ++j) {  // all loads first, then the compares
+        const int i = tid + NT * j;
+        const int px = i / nq, q = i - px * nq;
+        const int oy = oy0 + px / TW, ox = ox0 + px % TW;
+        gv[j] = make_float4(nan, nan, nan, nan);
+        if (i < items && oy < p.Ho && ox < p.Wo)
+          gv[j] = *(const float4*)(p.gate + (((size_t)b * p.Ho + oy) * p.Wo + ox) * p.pw_ys + 4 * q);
+      }
+      int any = 0;
+#pragma unroll
+      for (int j = 0; j < GJ; ++j) any |= gv[j].x >= gm || gv[j].y >= gm || gv[j].z >= gm || gv[j].w >= gm;
+      if (!__syncthreads_or(any)) return;
+    }
+  }
 
   // raw buffer loads: out-of-range offsets (halo outside the map, channels past Cin, weight rows past
   // Cout_pad) read zeros; host: both tensors < 2 GiB (x3hg_supported)
@@ -619,7 +646,10 @@ bool x3hg_pw_supported(const ConvParams& p, int bn, int pwn) {
   return p.w3 != nullptr && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.Cin % 4 == 0 && p.xs % 4 == 0 &&
          (size_t)p.B * p.H * p.W * p.xs * 4 < (1u << 31) - (1u << 20) && p.Cout % 4 == 0 && p.Cout_pad <= bn &&
          p.res == nullptr && p.y2 == nullptr && p.lb_meta == nullptr && p.pw_w != nullptr && p.pw_y != nullptr &&
-         p.pw_kpad == bn && p.pw_cout % 4 == 0 && p.pw_cout <= 32 * pwn && p.pw_ys % 4 == 0;
+         p.pw_kpad == bn && p.pw_cout % 4 == 0 && p.pw_cout <= 32 * pwn && p.pw_ys % 4 == 0 &&
+         (p.gate == nullptr ||  // the gate's float4 reads: 16-byte aligned, inside a pixel's pw_ys elements
+          (p.gate_n > 0 && p.gate_n <= HG_GATE_MAX_N && p.gate_n % 4 == 0 && p.gate_n <= p.pw_ys &&
+           (uintptr_t)p.gate % 16 == 0));
 }
 
 bool conv_x3hg_pw(const ConvParams& p, hipStream_t s, int v) {

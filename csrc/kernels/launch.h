@@ -48,6 +48,14 @@ struct ConvParams {
   const float* pw_bias; // fp32 [pw_cout_pad]
   void* pw_y;           // bf16 output, pixel stride pw_ys
   int pw_ys, pw_cout, pw_kpad, pw_act;
+  // Optional tile gate (x3hg fused-1x1 kernels only, every other conv kernel ignores it; nullptr = off): fp32
+  // logits with the pixel indexing and pixel stride of pw_y.  A workgroup whose in-map tile pixels hold no
+  // logit >= gate_min among their first gate_n channels (a multiple of 4, 16-byte aligned) returns before it
+  // loads anything else and writes nothing (NaN compares false); a tile that continues is computed as without
+  // the gate.  The Detect head's box branch is gated by the class logits of its level (runtime/head_gate.h).
+  const float* gate;
+  int gate_n;
+  float gate_min;
   // Letterbox source (fp32 x3-h16 stem only): when lb_meta is set the input is not read from x but sampled
   // from the batch's uint8 images (letterbox.h), H x W being the space-to-depth grid (T / 2) of the target.
   const uint8_t* lb_pool;

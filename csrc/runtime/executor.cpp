@@ -33,7 +33,17 @@ float bits_to_float(int64_t v) {
 }
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 constexpr size_t kCtrlBytes = 256;
+static_assert(kHgOpConv == OP_CONV && kHgOpDecode == OP_DECODE && kHgDtypeField == kDtypeField &&
+                  sizeof(OpRecord) == sizeof(int64_t) * kOpFields,
+              "head_gate.h reads the executor's op records");
+bool g_head_gate = [] {
+  const char* e = std::getenv("ARENA_HEAD_GATE");
+  return e == nullptr || std::atoi(e) != 0;
+}();
 }  // namespace
+
+void set_head_gate(bool v) { g_head_gate = v; }
+bool get_head_gate() { return g_head_gate; }
 
 Executor::Executor(const ExecutorConfig& cfg) : cfg_(cfg) {
   if (cfg_.max_batch <= 0 || cfg_.max_batch > 1024) throw std::runtime_error("Executor: max_batch out of range");
@@ -291,6 +301,7 @@ void Executor::set_program(const int64_t* ops, int n_ops, const int64_t* cls_ops
     for (int f = 1; f < kOpFields; ++f) has_raw_ |= r[f] == BUF_RAWOUT && (r[0] == OP_YOLORAW || r[0] == OP_CONV);
   }
   if (has_raw_ && cfg_.raw_out_bytes <= 0) throw std::runtime_error("program exports raw outputs: raw_out_bytes = 0");
+  gate_pairs_ = head_gate_pairs(prog_.empty() ? nullptr : prog_[0].data(), n_ops, kOpFields);
 }
 
 int Executor::crop_cap_for(int B) const { return std::max(cfg_.min_crop_cap, B * cfg_.crop_cap_per_image); }
@@ -513,11 +524,23 @@ void Executor::capture(Bucket& bk, int s) {
   // Validate the program eagerly once (launch errors surface here, not in the graph).
   ARENA_HIP_CHECK(hipStreamSynchronize(st));
   destroy_graphs(bk, s);
+  if (s == 0) {
+    bk.exec_order.clear();
+    bk.gated.clear();
+  }
   // One capture of ops [a, b) on the slot's stream.  The result D2H copy is issued after the graph launch, not
   // captured: a captured device->pinned-host memcpy node faulted on ROCm 7.0 (torch's runtime) while the same
   // graph without it runs cleanly.
   auto capture_range = [&](size_t a, size_t b) {
     std::vector<OpRecord> part(prog_.begin() + a, prog_.begin() + b);
+    if (s == 0) {  // every slot captures the same order
+      std::vector<const HeadGatePair*> gate;
+      const std::vector<size_t> order = exec_plan(part, bk, (int)a, 0, gate);
+      for (size_t k = 0; k < order.size(); ++k) {
+        bk.exec_order.push_back((int)(a + order[k]));
+        if (gate[k] != nullptr) bk.gated.push_back((int)(a + order[k]));
+      }
+    }
     hipGraph_t g = nullptr;
     hipGraphExec_t ge = nullptr;
     ARENA_HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
@@ -642,6 +665,36 @@ uint8_t* Executor::resolve(Bucket& bk, Slot& sl, int64_t buf, int64_t coff, int 
   return base + coff * eb;
 }
 
+// Head gate (head_gate.h): a pair's class conv (op i + 1) is enqueued before its box conv (op i), which then skips
+// the tiles without a passing class logit.  Swapping the two cannot break the arena layout: they are adjacent and
+// independent, so the buffers of both are live across both positions in either order.  A pair stays in program
+// order and ungated when its two ops are not both in this enqueue segment (a stagger split point or a lane boundary
+// between them, a single op of the debug modes), when an op is being timed (force_impl: timings stay dense-cost, and
+// the logits buffer holds nothing meaningful then) and when the kernel chosen for the box conv is not an x3hg
+// fused-1x1 variant.  The gate is advisory: an ungated op is merely slower, never wrong.
+std::vector<size_t> Executor::exec_plan(const std::vector<OpRecord>& prog, const Bucket& bk, int op_offset,
+                                        int force_impl, std::vector<const HeadGatePair*>& gate) const {
+  std::vector<size_t> order(prog.size());
+  for (size_t k = 0; k < order.size(); ++k) order[k] = k;
+  gate.assign(prog.size(), nullptr);
+  if (!g_head_gate || force_impl != 0) return order;
+  for (const HeadGatePair& gp : gate_pairs_) {
+    const long li = (long)gp.box - op_offset;
+    float gm;
+    if (li < 0 || li + 1 >= (long)prog.size() || gp.cls >= (int)prog_.size()) continue;
+    if (!head_gate_min(gp.conf_thr, &gm)) continue;  // a threshold outside the gate's range
+    if (prog[li] != prog_[gp.box] || prog[li + 1] != prog_[gp.cls]) continue;  // not that slice of prog_
+    const int impl = gp.box < (int)bk.impl.size() ? bk.impl[gp.box] : 0;
+    const bool x3hg_pw = impl == 0 || (impl >= kF32X3HGPw && impl < kF32X3HGPw + kF32X3HGPwVariants) ||
+                         (impl >= kF32X3HGPwSmall && impl < kF32X3HGPwSmall + kF32X3HGPwSmallVariants);
+    if (!x3hg_pw) continue;
+    order[li] = (size_t)li + 1;
+    order[li + 1] = (size_t)li;
+    gate[li + 1] = &gp;
+  }
+  return order;
+}
+
 void Executor::enqueue_program(const std::vector<OpRecord>& prog, Bucket& bk, Slot& sl, hipStream_t s_main,
                                int op_offset, int force_impl) {
   Ctrl* ctrl = (Ctrl*)resolve(bk, sl, BUF_CTRL, 0, 1);
@@ -654,7 +707,10 @@ void Executor::enqueue_program(const std::vector<OpRecord>& prog, Bucket& bk, Sl
 
   // Lane ops (kLaneField) run in program order here: the lanes' side streams are driven by launch_graph() over
   // per-lane captured segments, not by forking inside one capture.
-  for (size_t oi = 0; oi < prog.size(); ++oi) {
+  std::vector<const HeadGatePair*> gate;
+  const std::vector<size_t> order = exec_plan(prog, bk, op_offset, force_impl, gate);
+  for (size_t k = 0; k < prog.size(); ++k) {
+    const size_t oi = order[k];
     const OpRecord& r = prog[oi];
     hipStream_t s = s_main;
     // field 47: activation precision of the op (0 bf16, 1 exact fp32; planner.OP_DTYPE_FIELD)
@@ -715,6 +771,11 @@ void Executor::enqueue_program(const std::vector<OpRecord>& prog, Bucket& bk, Sl
           p.pw_ys = (int)r[38];
           p.pw_act = (int)r[39];
           if (!f32) p.impl = 2;  // bf16: the v3 halo-tile kernel; fp32: the tuned x3hg-pw variant
+          if (gate[k] != nullptr) {  // box conv of a head-gate pair: the level's class logits, already enqueued
+            p.gate = (const float*)resolve(bk, sl, r[36], r[37] + kHeadBoxChannels, eb);
+            p.gate_n = kHeadClsChannels;
+            head_gate_min(gate[k]->conf_thr, &p.gate_min);
+          }
         }
         if (f32)
           conv2d_f32(p, s);

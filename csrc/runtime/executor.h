@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "../kernels/launch.h"
+#include "head_gate.h"
 #include "instance.h"
 
 namespace arena {
@@ -50,6 +51,12 @@ constexpr int kMaxSlots = 6;
 constexpr int kMaxStaggerParts = 5;  // staggered launch: at most 4 split points (executor.cpp launch_graph)
 constexpr int kMaxEstBuckets = 257;  // completion-time estimates per bucket size (larger buckets share the last)
 using OpRecord = std::array<int64_t, kOpFields>;
+
+// ARENA_HEAD_GATE (default 1): in fp32 programs that end in DECODE, the Detect head's fused box convs skip the tiles
+// whose class logits all fail the confidence threshold (head_gate.h; enqueue_program).  Read when a bucket is
+// captured: a change applies to buckets added after it.
+void set_head_gate(bool v);
+bool get_head_gate();
 
 enum OpType : int64_t {
   OP_CONV = 1,
@@ -243,6 +250,9 @@ class Executor : public BatchInstance {
     };
     std::vector<Seg> segs[kMaxSlots];
     std::vector<int16_t> impl;  // per op of prog_: conv kernel family chosen by autotune (0 = default)
+    // the captured graphs' kernels in launch order, as indices into prog_ (program order except for the swapped
+    // head-gate pairs), and the ops that run with a tile gate
+    std::vector<int> exec_order, gated;
   };
 
   void alloc_slots();
@@ -261,8 +271,21 @@ class Executor : public BatchInstance {
   void enqueue_program(const std::vector<OpRecord>& prog, Bucket& bk, Slot& sl, hipStream_t s,
                        int op_offset = 0, int force_impl = 0);
   void autotune(Bucket& bk);
+  // Positions of `prog` (ops [op_offset, op_offset + size) of prog_) in the order they are enqueued; gate[k], when
+  // not null, is the head-gate pair whose box conv is enqueued k-th
+  std::vector<size_t> exec_plan(const std::vector<OpRecord>& prog, const Bucket& bk, int op_offset, int force_impl,
+                                std::vector<const HeadGatePair*>& gate) const;
 
  public:
+  // ops of prog_ in the order bucket B's graphs run them, and those among them that run with a tile gate
+  std::vector<int> exec_order(int B) const {
+    auto it = buckets_.find(B);
+    return it == buckets_.end() ? std::vector<int>{} : it->second.exec_order;
+  }
+  std::vector<int> gated_ops(int B) const {
+    auto it = buckets_.find(B);
+    return it == buckets_.end() ? std::vector<int>{} : it->second.gated;
+  }
   // conv kernel family per program op chosen for bucket B (0 = default / not a conv)
   std::vector<int> conv_choices(int B) const {
     auto it = buckets_.find(B);
@@ -293,6 +316,7 @@ class Executor : public BatchInstance {
   uint8_t* d_weights_ = nullptr;
   size_t weights_bytes_ = 0;
   std::vector<OpRecord> prog_, cls_prog_;
+  std::vector<HeadGatePair> gate_pairs_;  // head_gate_pairs(prog_)
   std::map<int, Bucket> buckets_;
   Slot slots_[kMaxSlots];
   int n_slots_ = 2;

@@ -46,11 +46,16 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, stride: in
                 x_coff: int = 0, cin: int | None = None, out: torch.Tensor | None = None, out_coff: int = 0,
                 res: torch.Tensor | None = None, res_coff: int = 0, out2: torch.Tensor | None = None,
                 out2_coff: int = 0, f32out: bool = False, out_hw=None, bdev: torch.Tensor | None = None,
-                packed=None, impl: int = 0, pw=None) -> torch.Tensor:
+                packed=None, impl: int = 0, pw=None, pw_out: torch.Tensor | None = None, pw_out_coff: int = 0,
+                gate=None) -> torch.Tensor:
     """NHWC conv with fused bias/act/residual/upsampled copy.
 
     ``pw=(w2, b2)`` (fp32 3x3 stride-1 only): the Detect-head 1x1 ``w2`` [C2, Cout, 1, 1] is applied to the
-    activated result inside the x3hg epilogue (impl 145 + v) and only its [B, Ho, Wo, C2] output is returned.
+    activated result inside the x3hg epilogue (impl 145 + v) and only its [B, Ho, Wo, C2] output is returned;
+    ``pw_out`` (float32 [B, Ho, Wo, C], optional): write those C2 channels at ``pw_out_coff`` of it instead and
+    return it.  ``gate=(logits, coff, n, gate_min)`` (x3hg fused-1x1 kernels only): float32 ``logits`` with the shape
+    of the tensor the 1x1 output is written to; a tile none of whose pixels has ``logits[..., coff:coff + n] >=
+    gate_min`` is skipped and keeps its previous contents (ConvParams.gate).
 
     x: [B, H, W, Cx] bf16 or float32 (reads channels [x_coff, x_coff + Cin)); w: [Cout, Cin, KH, KW] fp32.
     A float32 ``x`` runs the exact-fp32 kernel (fp32 weights, v_mfma_f32_16x16x4_f32, fp32 output).
@@ -89,9 +94,24 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, stride: in
         b2p = torch.zeros((co2 + 15) // 16 * 16)
         b2p[:co2] = b2.detach().float()
         b2p = b2p.to(x.device)
-        out = torch.empty(B, Ho, Wo, co2, dtype=torch.float32, device=x.device)
-        pwd = {"pw_w": _ptr(w2p), "pw_bias": _ptr(b2p), "pw_y": _ptr(out), "pw_ys": co2, "pw_cout": co2,
-               "pw_kpad": k2, "pw_act": 0}
+        if pw_out is None:
+            out = torch.empty(B, Ho, Wo, co2, dtype=torch.float32, device=x.device)
+            pw_out_coff = 0
+        else:
+            out = pw_out
+            if (out.shape[:3] != (B, Ho, Wo) or out.shape[3] < pw_out_coff + co2 or out.dtype != torch.float32
+                    or out.device != x.device or not out.is_contiguous()):
+                raise ValueError(f"conv2d_nhwc: pw_out {tuple(out.shape)} {out.dtype} does not fit the 1x1 output")
+        pwd = {"pw_w": _ptr(w2p), "pw_bias": _ptr(b2p), "pw_y": _ptr(out, pw_out_coff), "pw_ys": out.shape[-1],
+               "pw_cout": co2, "pw_kpad": k2, "pw_act": 0}
+        if gate is not None:
+            gt, gcoff, gn, gmin = gate
+            if (gt.shape != out.shape or gt.dtype != torch.float32 or gt.device != x.device or not gt.is_contiguous()
+                    or gcoff < 0 or gn <= 0 or gcoff + gn > gt.shape[3]):
+                raise ValueError("conv2d_nhwc: the gate logits must match the 1x1 output tensor's shape and stride")
+            pwd.update({"gate": _ptr(gt, gcoff), "gate_n": int(gn), "gate_min": float(gmin)})
+    elif gate is not None or pw_out is not None:
+        raise ValueError("conv2d_nhwc: gate / pw_out need pw")
     skd = {}
     if 171 <= int(impl) < 180:  # split-K x3g: a workspace for the partial tiles (splits <= 8)
         ws = torch.empty(8 * B * Ho * Wo * cpad, dtype=torch.float32, device=x.device)

@@ -66,6 +66,8 @@ class Settings(BaseModel):
     # kernel switch the native library reads from the process environment when it loads (listed here so that the
     # .env template's key is a known setting): 1 K-packed x3 kernel for fp32 MobileNetV2 block 2, 0 the exact-fp32 one
     ARENA_IR_S2K16: int = 1
+    # likewise read natively: 1 the fp32 Detect head's box convs skip tiles without a passing class logit, 0 dense
+    ARENA_HEAD_GATE: int = 1
 
     @classmethod
     def from_env(cls, env_file: str | Path = ".env", **overrides) -> "Settings":

@@ -142,7 +142,7 @@ def duration_check(vals: dict[int, dict[str, list[float]]], dur_pmc: dict[int, l
 def main(argv=None) -> int:
     from inference_arena_amd.engine.plans import plan_pipeline
     from inference_arena_amd.models.zoo import default_models
-    from tools.analyze_trace import KIND, describe
+    from tools.analyze_trace import KIND, describe, load_order
 
     ap = argparse.ArgumentParser()
     ap.add_argument("csvs", nargs="+")
@@ -152,6 +152,9 @@ def main(argv=None) -> int:
     ap.add_argument("--times", required=True,
                     help="per-op table of analyze_trace.py for the same program: kernel names (attribution) and "
                          "un-profiled durations (duration check, TB/s)")
+    ap.add_argument("--order", default=None,
+                    help="executed op order of the profiled bucket (profile_engine.py --order-out): dispatch k of a "
+                         "replay is op order[k]")
     ap.add_argument("--tol", type=float, default=0.30)
     ap.add_argument("--no-check", action="store_true", help="report duration disagreements without failing")
     a = ap.parse_args(argv)
@@ -162,19 +165,22 @@ def main(argv=None) -> int:
         print(f"op table lists ops {min(tnames, default=-1)}..{max(tnames, default=-1)}, program has {n_ops}",
               file=sys.stderr)
         return 2
+    order = load_order(a.order, n_ops)
     expected = [tnames[k] for k in range(n_ops)]
+    expected_run = [tnames[order[pos]] for pos in range(n_ops)]  # kernel names in launch order
     problems = []
     vals: dict[int, dict[str, list[float]]] = defaultdict(lambda: defaultdict(list))
     per_set = []
     for f in a.csvs:
-        reps = find_replays(load_dispatches(Path(f)), expected, a.replays)
+        reps = find_replays(load_dispatches(Path(f)), expected_run, a.replays)
         if not reps:
             problems.append(f"{f}: no window of dispatches matches the op table's kernel sequence")
             continue
         sv: dict[int, dict[str, list[float]]] = defaultdict(lambda: defaultdict(list))
         dur: dict[int, list[float]] = defaultdict(list)
         for rp in reps:
-            for k, d in enumerate(rp):
+            for pos, d in enumerate(rp):
+                k = order[pos]
                 for c, v in d["counters"].items():
                     vals[k][c].append(v)
                     sv[k][c].append(v)

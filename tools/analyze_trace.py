@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """Map a rocprofv3 kernel trace of the executor back to program ops.
 
-The executor's hipGraph replays the program's ops in order, one kernel per
-op, so the k-th arena kernel of each replay is op k.  This tool takes the last
+The executor's hipGraph replays the program's ops one kernel per op, in
+program order except for the Detect head's gated pairs, whose class conv runs
+before its box conv: the k-th arena kernel of each replay is op ``order[k]``,
+``order`` being the executed order the executor reports (``--order``, written
+by tools/profile_engine.py ``--order-out``; without it, program order).  This tool takes the last
 ``--replays`` complete replays from ``*_kernel_trace.csv``, averages each op's
 duration and prints a per-op table (op index, kind, layer shape, kernel
 variant, VGPRs, grid, mean us, share) plus per-kind totals.
@@ -58,6 +61,18 @@ def first_kernel(op0) -> str:
     return first
 
 
+def load_order(path, n_ops: int) -> list[int]:
+    """Executed order (tools/profile_engine.py --order-out): position in a replay -> program op; None: program order."""
+    if not path:
+        return list(range(n_ops))
+    import json
+
+    order = [int(v) for v in json.loads(Path(path).read_text())["exec_order"]]
+    if sorted(order) != list(range(n_ops)):
+        raise SystemExit(f"{path}: not a permutation of the program's {n_ops} ops")
+    return order
+
+
 def merge_split_k(q: list[dict]) -> list[dict]:
     """One queue's dispatches in start order, with each split-K conv's second kernel (gemm_x3.hip, impl 171+: the
     partial GEMM, then x3g_sk_reduce_kernel) folded into its op: the reduce's time is added to the GEMM row
@@ -81,6 +96,7 @@ def main(argv=None) -> int:
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None, help="write the table as markdown")
     ap.add_argument("--dtype", default="bf16", help="program precision the trace was taken with")
+    ap.add_argument("--order", default=None, help="executed op order of the traced bucket (profile_engine.py --order-out)")
     a = ap.parse_args(argv)
 
     from inference_arena_amd.engine.plans import plan_pipeline
@@ -88,6 +104,8 @@ def main(argv=None) -> int:
 
     prog = plan_pipeline(*default_models(a.seed), conf_thr=0.5, iou_thr=0.45, dtype=a.dtype)
     n_ops = prog.ops.shape[0]
+    order = load_order(a.order, n_ops)
+    pos_of = {op: k for k, op in enumerate(order)}
     rows = [r for r in csv.DictReader(open(a.trace)) if "arena::" in r["Kernel_Name"]]
     # the executor runs each staging slot on its own stream: slice replays per hardware queue so that
     # kernels of concurrently running graphs are not interleaved
@@ -95,7 +113,7 @@ def main(argv=None) -> int:
     by_q = defaultdict(list)
     for r in rows:
         by_q[r[qkey] if qkey else 0].append(r)
-    first = first_kernel(prog.ops[0])
+    first = first_kernel(prog.ops[order[0]])
     replays = []
     for qk in list(by_q):
         by_q[qk] = merge_split_k(sorted(by_q[qk], key=lambda r: int(r["Start_Timestamp"])))
@@ -103,6 +121,10 @@ def main(argv=None) -> int:
         starts = [i for i, r in enumerate(q) if first in r["Kernel_Name"]]
         replays += [q[s:s + n_ops] for s in starts if s + n_ops <= len(q)]
     replays = [rp for rp in replays if len(rp) == n_ops]
+    # a program with several stamp ops starts a window at each of them, and overflow classification passes put
+    # further kernels between replays: keep the windows whose stamp kernels sit exactly at the program's stamp ops
+    is_stamp = [int(prog.ops[order[pos]][0]) == 18 for pos in range(n_ops)]
+    replays = [rp for rp in replays if [("stamp_kernel" in r["Kernel_Name"]) for r in rp] == is_stamp]
     replays.sort(key=lambda rp: int(rp[0]["Start_Timestamp"]))
     # keep replays whose kernel sequence matches the program's final one (drops slices that straddle
     # autotuning / overflow passes), then use per-op medians
@@ -115,14 +137,15 @@ def main(argv=None) -> int:
         return 1
     dur = defaultdict(list)
     for rp in replays:
-        for k, r in enumerate(rp):
+        for pos, r in enumerate(rp):
+            k = order[pos]
             dur[k].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) + r.get("_extra_ns", 0)) / 1e3)
     med = {k: sorted(v)[len(v) // 2] for k, v in dur.items()}
     total = sum(med.values())
     lines = ["| op | kind | shape | kernel | vgpr | grid | mean us | share |", "|---|---|---|---|---|---|---|---|"]
     per_kind = defaultdict(float)
     for k in range(n_ops):
-        r = replays[-1][k]
+        r = replays[-1][pos_of[k]]
         us = med[k]
         kind = KIND.get(int(prog.ops[k][0]), "?")
         per_kind[kind] += us

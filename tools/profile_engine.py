@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Engine-only driver for rocprofv3: runs ``--batches`` full batches of the curated workload through
 one GpuPipeline (``--dtype``), sequentially, so a kernel trace maps one graph replay per batch onto
-the program's ops (tools/analyze_trace.py)."""
+the program's ops (tools/analyze_trace.py).  ``--order-out`` writes the order in which the bucket's graphs launch
+the program's ops (the executor swaps the Detect head's gated pairs) for the analysis tools' ``--order``."""
 from __future__ import annotations
 
 import argparse
@@ -21,7 +22,14 @@ def main(argv=None) -> int:
     ap.add_argument("--inputs", default="rgb", choices=["rgb", "jpeg"],
                     help="rgb: decoded frames (host pack); jpeg: the HTTP path's device inputs (JPEG q90 uploads "
                          "entropy-decoded once into pinned buffers: coefficient H2D + GPU reconstruction per batch)")
+    ap.add_argument("--conf-thr", type=float, default=None,
+                    help="detector confidence threshold (default: the configured one); a program the tuning table "
+                         "does not hold is tuned by timing unless ARENA_TUNING=off")
+    ap.add_argument("--order-out", default=None,
+                    help="write {bucket, exec_order, gated} as JSON here (put it next to the trace)")
     a = ap.parse_args(argv)
+    import json
+
     import torch
 
     from inference_arena_amd.data.curator import DatasetManifest, load_manifest_images
@@ -32,8 +40,14 @@ def main(argv=None) -> int:
     sfx = "" if a.dtype == "fp32" else f"_{a.dtype}"
     man = DatasetManifest.load(root / "data" / "synthetic_set" / f"manifest_w{a.seed}_n100{sfx}.json")
     images = load_manifest_images(man)
-    pipe = GpuPipeline(*default_models(a.seed), device=0, buckets=[a.batch], dtype=a.dtype)
+    pipe = GpuPipeline(*default_models(a.seed), device=0, buckets=[a.batch], dtype=a.dtype, conf_thr=a.conf_thr)
     B = a.batch
+    if a.order_out:
+        n_ops = int(pipe.program.ops.shape[0])
+        order = list(pipe.ex.exec_order(B)) if hasattr(pipe.ex, "exec_order") else list(range(n_ops))
+        gated = list(pipe.ex.gated_ops(B)) if hasattr(pipe.ex, "gated_ops") else []
+        Path(a.order_out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.order_out).write_text(json.dumps({"bucket": B, "exec_order": order, "gated": gated}) + "\n")
     if a.inputs == "jpeg":
         from inference_arena_amd.data.synthetic import encode_jpeg
         from inference_arena_amd.ops import native
