@@ -93,6 +93,12 @@ void py_conv2d(const py::dict& d) {
   p.gate = ptr<const float*>(d, "gate");
   p.gate_n = get<int>(d, "gate_n", 0);
   p.gate_min = get<float>(d, "gate_min", 0.f);
+  p.n_lo = get<int>(d, "n_lo", 0);
+  p.n_hi = get<int>(d, "n_hi", 0);
+  p.marks = ptr<const int*>(d, "marks");
+  p.mark_uh = get<int>(d, "mark_uh", 0);
+  p.mark_uw = get<int>(d, "mark_uw", 0);
+  p.mark_halo = get<int>(d, "mark_halo", 0);
   p.w3 = ptr<const void*>(d, "w3");
   p.sk_ws = ptr<float*>(d, "sk_ws");
   p.sk_ws_bytes = get<int64_t>(d, "sk_ws_bytes", 0);
@@ -101,6 +107,30 @@ void py_conv2d(const py::dict& d) {
     conv2d_f32(p, stream_of(d));
   else
     conv2d(p, stream_of(d));
+}
+
+void py_head_mark(const py::dict& d) {
+  HeadMarkParams p{};
+  const std::vector<uintptr_t> logits = req<std::vector<uintptr_t>>(d, "logits");
+  const std::vector<uintptr_t> marks = req<std::vector<uintptr_t>>(d, "marks");
+  const std::vector<int> H = req<std::vector<int>>(d, "H"), W = req<std::vector<int>>(d, "W");
+  const std::vector<int> ps = req<std::vector<int>>(d, "ps");
+  const size_t n = logits.size();
+  if (n < 1 || n > (size_t)kMarkMaxLevels || marks.size() != n || H.size() != n || W.size() != n || ps.size() != n)
+    throw std::runtime_error("head_mark: 1..3 levels, one entry per level in every list");
+  p.n_levels = (int)n;
+  for (size_t l = 0; l < n; ++l) {
+    p.logits[l] = reinterpret_cast<const float*>(logits[l]);
+    p.marks[l] = reinterpret_cast<int*>(marks[l]);
+    p.H[l] = H[l];
+    p.W[l] = W[l];
+    p.ps[l] = ps[l];
+  }
+  p.n = req<int>(d, "n");
+  p.gate_min = req<float>(d, "gate_min");
+  p.B = req<int>(d, "B");
+  p.bdev = ptr<const int*>(d, "bdev");
+  head_mark(p, stream_of(d));
 }
 
 void py_dwconv(const py::dict& d) {
@@ -640,6 +670,43 @@ PYBIND11_MODULE(_C, m) {
         return out;
       },
       py::arg("ops"), "[(box conv op, class conv op, level)] of a program's records");
+  // Head split (runtime/head_marks.h)
+  m.def("set_head_split", &set_head_split);
+  m.def("get_head_split", &get_head_split);
+  m.attr("HEAD_SPLIT_MIN_BUCKET") = kHeadSplitMinBucket;
+  m.attr("HEAD_SPLIT_BOX_IMPL") = kF32X3HP + kHeadSplitBoxVariant;
+  m.attr("HEAD_SPLIT_CLS_IMPL") = kF32X3HP + kHeadSplitClsVariant;
+  m.attr("MARK_CELL") = kMarkCell;
+  m.def("head_mark", &py_head_mark);
+  m.def(
+      "head_gate_first_convs",
+      [](py::array_t<int64_t, py::array::c_style> ops) {
+        if (ops.ndim() != 2 || ops.shape(1) != kOpFields) throw std::runtime_error("ops must be int64 [n, OP_FIELDS]");
+        py::list out;
+        for (const HeadGatePair& gp : head_gate_pairs(ops.data(), (int)ops.shape(0), kOpFields))
+          out.append(head_gate_first_conv(ops.data(), (int)ops.shape(0), kOpFields, gp));
+        return out;
+      },
+      py::arg("ops"), "per head-gate pair of a program's records: the op of its first head conv, or -1");
+  m.def(
+      "head_marks_needed",
+      [](py::array_t<int, py::array::c_style | py::array::forcecast> marks, int H, int W, int th, int tw, int uh,
+         int uw, int halo) {
+        if (H <= 0 || W <= 0 || th <= 0 || tw <= 0 || uh <= 0 || uw <= 0 || halo < 0 || marks.ndim() != 2 ||
+            marks.shape(0) != head_mark_cells(H) || marks.shape(1) != head_mark_cells(W))
+          throw std::runtime_error("head_marks_needed: marks must be int32 [ceil(H / 8), ceil(W / 8)], sizes > 0");
+        const int nty = (H + th - 1) / th, ntx = (W + tw - 1) / tw;
+        py::array_t<bool> out({nty, ntx});
+        auto o = out.mutable_unchecked<2>();
+        for (int ty = 0; ty < nty; ++ty)
+          for (int tx = 0; tx < ntx; ++tx)
+            o(ty, tx) = head_marks_needed(marks.data(), H, W, ty, tx, th, tw, uh, uw, halo);
+        return out;
+      },
+      py::arg("marks"), py::arg("H"), py::arg("W"), py::arg("th"), py::arg("tw"), py::arg("uh"), py::arg("uw"),
+      py::arg("halo"),
+      "bool [tiles_y, tiles_x]: the th x tw producer tiles of one image that a continuing uh x uw consumer tile, "
+      "grown by halo pixels, reads (the host oracle of the x3hp mark gate)");
   m.attr("HEAD_BOX_CHANNELS") = kHeadBoxChannels;
   m.attr("HEAD_CLS_CHANNELS") = kHeadClsChannels;
   m.def("letterbox_s2d", &py_letterbox);
@@ -826,6 +893,9 @@ PYBIND11_MODULE(_C, m) {
       .def("exec_order", &Executor::exec_order, py::arg("B"),
            "program op indices in the order bucket B's graphs launch them")
       .def("gated_ops", &Executor::gated_ops, py::arg("B"), "ops of bucket B that run with a tile gate")
+      .def("launch_order", &Executor::launch_order, py::arg("B"),
+           "every kernel launch of bucket B's graphs in order as (op, kind): 0 the whole op, 1 / 2 the class / "
+           "box window of a split first head conv, 3 the cell marks launched before op's box conv")
       .def("stream", &Executor::stream);
 
   py::class_<SplitInstance, std::shared_ptr<SplitInstance>>(m, "SplitInstance")

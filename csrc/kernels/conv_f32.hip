@@ -1578,17 +1578,16 @@ void conv2d_f32(const ConvParams& p, hipStream_t s) {
     throw std::runtime_error("conv2d_f32: unsupported geometry (Cin/xs/ys %4, Kpad %16, Cout_pad %16, Cout %4)");
   if (p.Cin < 16) throw std::runtime_error("conv2d_f32: Cin must be >= 16");
   if (p.Kpad < p.KH * p.KW * p.Cin) throw std::runtime_error("conv2d_f32: Kpad < KH*KW*Cin");
+  if ((p.n_lo != 0 || p.n_hi != 0 || p.marks != nullptr) &&
+      !(p.pw_w == nullptr && p.impl >= kF32X3HP && p.impl < kF32X3HP + kF32X3HPVariants))
+    throw std::runtime_error("conv2d_f32: an output-channel window or a mark gate needs an x3hp variant");
   if (p.pw_w != nullptr) {  // fused Detect-head 1x1: only the x3hg epilogue variants implement it
     if (p.impl >= kF32X3HRPw && p.impl < kF32X3HRPw + kF32X3HRPwVariants) {
       if (!conv_x3hr_pw(p, s, p.impl - kF32X3HRPw))
         throw std::runtime_error("conv2d_f32: a fused pointwise epilogue needs an x3hr-pw variant that fits the conv");
       return;
     }
-    const int v = p.impl >= kF32X3HGPw && p.impl < kF32X3HGPw + kF32X3HGPwVariants ? p.impl - kF32X3HGPw
-                  : p.impl >= kF32X3HGPwSmall && p.impl < kF32X3HGPwSmall + kF32X3HGPwSmallVariants
-                      ? kF32X3HGPwVariants + p.impl - kF32X3HGPwSmall
-                  : p.impl == 0 ? (p.Cout_pad <= 64 ? 0 : 2)
-                                : -1;
+    const int v = x3hg_pw_variant(p.impl, p.Cout_pad);
     if (v < 0 || !conv_x3hg_pw(p, s, v))
       throw std::runtime_error("conv2d_f32: a fused pointwise epilogue needs an x3hg-pw variant that fits the conv");
     return;

@@ -652,6 +652,24 @@ bool x3hg_pw_supported(const ConvParams& p, int bn, int pwn) {
            (uintptr_t)p.gate % 16 == 0));
 }
 
+int x3hg_pw_variant(int impl, int cout_pad) {
+  return impl >= kF32X3HGPw && impl < kF32X3HGPw + kF32X3HGPwVariants ? impl - kF32X3HGPw
+         : impl >= kF32X3HGPwSmall && impl < kF32X3HGPwSmall + kF32X3HGPwSmallVariants
+             ? kF32X3HGPwVariants + impl - kF32X3HGPwSmall
+         : impl == 0 ? (cout_pad <= 64 ? 0 : 2)
+                     : -1;
+}
+
+bool x3hg_pw_tile(int impl, int cout_pad, int* th, int* tw) {
+  switch (x3hg_pw_variant(impl, cout_pad)) {
+#define HG_PW_TILE(V, TW, WM, TM, TN, PWN) \
+  case V: *th = hg_th(TW, WM, TM); *tw = TW; return true;
+    HG_PW_VARIANTS(HG_PW_TILE)
+#undef HG_PW_TILE
+    default: return false;
+  }
+}
+
 bool conv_x3hg_pw(const ConvParams& p, hipStream_t s, int v) {
   switch (v) {
 #define HG_PW_CASE(V, TW, WM, TM, TN, PWN) \

@@ -19,6 +19,14 @@
 //     Detect-head convs (NF 9: 32 KB of weights per stage) so that their halo is staged and split once, not
 //     once per 48-channel tile.
 //
+// Two optional additions for the split Detect-head convs (runtime/head_marks.h): an output-channel window
+// (ConvParams.n_lo / n_hi: the workgroup's first channel is n_lo + blockIdx.y * BN, the epilogue stops at n_hi, the
+// grid covers the window only; weight rows, bias and output addresses stay absolute) and a mark gate
+// (ConvParams.marks: a workgroup whose tile no continuing consumer tile reads returns before any load).  A tile that
+// runs computes exactly what it computes in the whole conv.  <5, 8, 1> holds the 80-channel class window on per-tap
+// stages: 58 KB of LDS, two workgroups per CU, where <5, 8, 3> needs 89 KB and runs one (117 vs 176 us for the
+// 80x80x64 class window at batch 32, profiles/r11_head_split/README.md).
+//
 // LDS rows: halo pixels [h 32 | m 32 | l 32 | 16 pad] bf16 = 224 B, weight rows TS x 96 + 16 bf16 = 608 / 224 B;
 // both pitches keep the ds_read_b128 fragment reads of 16 consecutive rows conflict-free (tools/lds_bank_model.py).
 // The next stage's global loads are issued before the current stage's MFMAs, as in the old kernel.
@@ -36,6 +44,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "../runtime/head_marks.h"
 #include "common.h"
 #include "launch.h"
 
@@ -84,8 +93,14 @@ __global__ __launch_bounds__(TH * 32) void conv_x3hp_kernel(const ConvParams p) 
   const int t = bx - b * tiles;
   const int ty = t / tiles_x, tx = t - ty * tiles_x;
   const int oy0 = ty * TH, ox0 = tx * HP_TW;
+  // ---- mark gate (ConvParams.marks): nothing reads this tile unless a continuing consumer tile touches it; before
+  // any halo or weight load.  Wave-uniform: at most 18 mark reads for 8 x 16 tiles on both sides.
+  if (p.marks != nullptr) {
+    const int* m = p.marks + (size_t)b * head_mark_cells(p.Ho) * head_mark_cells(p.Wo);
+    if (!head_marks_needed(m, p.Ho, p.Wo, ty, tx, TH, HP_TW, p.mark_uh, p.mark_uw, p.mark_halo)) return;
+  }
   const int iy0 = oy0 - p.pad_t, ix0 = ox0 - p.pad_l;
-  const int n0 = blockIdx.y * BN;
+  const int n0 = p.n_lo + blockIdx.y * BN;  // the launcher sets n_hi (the whole conv: [0, Cout))
   const int H = p.H, W = p.W, Cin = p.Cin;
 
   // raw buffer loads: out-of-range offsets (halo outside the map, channels past Cin, weight rows past
@@ -216,7 +231,7 @@ __global__ __launch_bounds__(TH * 32) void conv_x3hp_kernel(const ConvParams p) 
 #pragma unroll
   for (int j = 0; j < NF; ++j) {
     const int cb = n0 + j * 16 + kq * 4;
-    if (cb >= p.Cout) continue;
+    if (cb >= p.n_hi) continue;
     const float4 bias = *(const float4*)(p.bias + cb);
 #pragma unroll
     for (int f = 0; f < MF; ++f) {
@@ -248,10 +263,15 @@ __global__ __launch_bounds__(TH * 32) void conv_x3hp_kernel(const ConvParams p) 
 namespace {
 
 template <int NF, int TH, int TS>
-void hp_launch(const ConvParams& p, hipStream_t s) {
+void hp_launch(const ConvParams& p0, hipStream_t s) {
   constexpr int BN = NF * 16;
+  ConvParams p = p0;
+  const bool whole = p.n_lo == 0 && p.n_hi == 0;
+  if (whole) p.n_hi = p.Cout;
   const int tiles = ((p.Wo + HP_TW - 1) / HP_TW) * ((p.Ho + TH - 1) / TH);
-  dim3 grid((unsigned)(p.B * tiles), (unsigned)((p.Cout_pad + BN - 1) / BN));
+  // the whole conv covers the padded rows as before; a window covers [n_lo, n_hi) only
+  const int span = whole ? p.Cout_pad : p.n_hi - p.n_lo;
+  dim3 grid((unsigned)(p.B * tiles), (unsigned)((span + BN - 1) / BN));
   hipLaunchKernelGGL((conv_x3hp_kernel<NF, TH, TS>), grid, dim3(TH * 32), hp_lds_bytes(NF, TH, TS), s, p);
 }
 
@@ -265,7 +285,8 @@ void hp_launch(const ConvParams& p, hipStream_t s) {
   X(5, 3, 16, 3)  /* 16 x 16 px x  48 ch (109) */ \
   X(6, 4, 16, 3)  /* 16 x 16 px x  64 ch (108) */ \
   X(7, 9, 8, 1)   /*  8 x 16 px x 144 ch, per-tap stages: the halo staged once for a Detect-head pair */ \
-  X(8, 9, 16, 1)  /* 16 x 16 px x 144 ch, 8 waves */
+  X(8, 9, 16, 1)  /* 16 x 16 px x 144 ch, 8 waves */ \
+  X(9, 5, 8, 1)   /*  8 x 16 px x  80 ch, per-tap stages: the class window of a split Detect-head conv */
 
 }  // namespace
 
@@ -275,7 +296,13 @@ bool x3hp_supported(const ConvParams& p) {
   return p.w3 != nullptr && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.Cin % 4 == 0 && p.xs % 4 == 0 &&
          x_bytes < (1u << 31) - (1u << 20) && w_bytes < (1u << 31) - (1u << 20) && p.Cout % 4 == 0 &&
          p.Cout_pad % 16 == 0 && p.ys % 4 == 0 && (p.res == nullptr || p.rs % 4 == 0) &&
-         (p.y2 == nullptr || p.y2s % 4 == 0) && p.lb_meta == nullptr && p.pw_w == nullptr;
+         (p.y2 == nullptr || p.y2s % 4 == 0) && p.lb_meta == nullptr && p.pw_w == nullptr &&
+         // window: 16-aligned start, 4-aligned end inside the conv; (0, 0) = the whole conv
+         ((p.n_lo == 0 && p.n_hi == 0) ||
+          (p.n_lo >= 0 && p.n_lo % 16 == 0 && p.n_hi > p.n_lo && p.n_hi <= p.Cout && p.n_hi % 4 == 0)) &&
+         // marks: the consumer's tiles are whole cells, so that the cells of a tile are exactly its pixels
+         (p.marks == nullptr || ((uintptr_t)p.marks % 4 == 0 && p.mark_uh > 0 && p.mark_uw > 0 &&
+                                 p.mark_uh % kMarkCell == 0 && p.mark_uw % kMarkCell == 0 && p.mark_halo >= 0));
 }
 
 bool conv_x3hp(const ConvParams& p, hipStream_t s, int v) {

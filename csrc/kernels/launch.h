@@ -56,6 +56,15 @@ struct ConvParams {
   const float* gate;
   int gate_n;
   float gate_min;
+  // Optional output-channel window and mark gate (x3hp kernels only; conv2d_f32 throws when another kernel is asked
+  // for either).  Window: the call computes and stores only the output channels [n_lo, n_hi) (n_lo a multiple of
+  // 16; n_hi 0 = up to Cout); weight rows, bias and output addresses stay those of the whole conv.  Marks: one int per 8 x 8-pixel
+  // cell and image of the output map (runtime/head_marks.h).  A workgroup whose tile no continuing consumer tile of
+  // mark_uh x mark_uw pixels, grown by mark_halo pixels, reads (head_marks_needed) returns before it loads anything
+  // else and writes nothing; a tile that continues is computed as without the marks.
+  int n_lo, n_hi;
+  const int* marks;
+  int mark_uh, mark_uw, mark_halo;
   // Letterbox source (fp32 x3-h16 stem only): when lb_meta is set the input is not read from x but sampled
   // from the batch's uint8 images (letterbox.h), H x W being the space-to-depth grid (T / 2) of the target.
   const uint8_t* lb_pool;
@@ -133,10 +142,30 @@ constexpr int kF32X3HRPwVariants = 6;
 // x3hp: the 16x16x32 halo tiles of kF32X3Halo* over the pre-split weights (halo_x3p.hip), variant v; bit-identical
 // to impl 101 / 102 / 103 / 108 / 109 on every conv they take
 constexpr int kF32X3HP = 191;
-constexpr int kF32X3HPVariants = 9;
+constexpr int kF32X3HPVariants = 10;
 bool x3hp_supported(const ConvParams& p);
 bool conv_x3hp(const ConvParams& p, hipStream_t s, int v);  // false if the conv or variant is not supported
 void x3hp_prepare();
+// fused-1x1 x3hg variant (halo_x3g.hip HG_PW_VARIANTS) that conv2d_f32 runs for ConvParams.impl on a conv with
+// cout_pad padded output channels (kF32X3HGPw + v, kF32X3HGPwSmall + v, 0 = by channel count), -1: none; and its
+// pixel tile
+int x3hg_pw_variant(int impl, int cout_pad);
+bool x3hg_pw_tile(int impl, int cout_pad, int* th, int* tw);
+// Detect-head cell marks (head_mark.hip, runtime/head_marks.h): for each of n_levels maps of H[l] x W[l] pixels,
+// marks[l][image][cell] = 1 iff one of the n fp32 logits at logits[l] + pixel * ps[l] of an in-map pixel of the
+// 8 x 8 cell is >= gate_min, else 0; every cell of a live image is written, images at or past the live count are
+// not touched.  n must be 80 (the Detect head's classes), ps a multiple of 4, logits 16-byte aligned.
+struct HeadMarkParams {
+  int n_levels;
+  const float* logits[3];
+  int H[3], W[3], ps[3];
+  int* marks[3];
+  int n;
+  float gate_min;
+  int B;
+  const int* bdev;
+};
+void head_mark(const HeadMarkParams& p, hipStream_t s);  // throws on a geometry it does not take
 bool conv_x3hr(const ConvParams& p, hipStream_t s, int v);
 bool conv_x3hr_pw(const ConvParams& p, hipStream_t s, int v);
 bool conv_fc_f32(const ConvParams& p, hipStream_t s);

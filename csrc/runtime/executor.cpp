@@ -40,10 +40,16 @@ bool g_head_gate = [] {
   const char* e = std::getenv("ARENA_HEAD_GATE");
   return e == nullptr || std::atoi(e) != 0;
 }();
+int g_head_split = [] {
+  const char* e = std::getenv("ARENA_HEAD_SPLIT");
+  return e == nullptr ? 1 : std::max(0, std::min(2, std::atoi(e)));
+}();
 }  // namespace
 
 void set_head_gate(bool v) { g_head_gate = v; }
 bool get_head_gate() { return g_head_gate; }
+void set_head_split(int v) { g_head_split = std::max(0, std::min(2, v)); }
+int get_head_split() { return g_head_split; }
 
 Executor::Executor(const ExecutorConfig& cfg) : cfg_(cfg) {
   if (cfg_.max_batch <= 0 || cfg_.max_batch > 1024) throw std::runtime_error("Executor: max_batch out of range");
@@ -302,6 +308,9 @@ void Executor::set_program(const int64_t* ops, int n_ops, const int64_t* cls_ops
   }
   if (has_raw_ && cfg_.raw_out_bytes <= 0) throw std::runtime_error("program exports raw outputs: raw_out_bytes = 0");
   gate_pairs_ = head_gate_pairs(prog_.empty() ? nullptr : prog_[0].data(), n_ops, kOpFields);
+  gate_first_.clear();
+  for (const HeadGatePair& gp : gate_pairs_)
+    gate_first_.push_back(head_gate_first_conv(prog_[0].data(), n_ops, kOpFields, gp));
 }
 
 int Executor::crop_cap_for(int B) const { return std::max(cfg_.min_crop_cap, B * cfg_.crop_cap_per_image); }
@@ -340,7 +349,24 @@ void Executor::add_bucket(int B, const int64_t* offsets, int n_buffers, int64_t 
   bk.info.arena_bytes = arena_bytes;
   sync_slots();
   free_arenas(bk);
-  const size_t abytes = (size_t)std::max<int64_t>(arena_bytes, 256);
+  size_t abytes = align_up((size_t)std::max<int64_t>(arena_bytes, 256), 256);
+  // head split: the cell marks of every pair with a first conv live behind the slot's arena (B x cells ints each)
+  bk.marks_off.assign(gate_pairs_.size(), -1);
+  for (size_t i = 0; i < gate_pairs_.size(); ++i) {
+    if (gate_first_[i] < 0) continue;
+    const OpRecord& f = prog_[gate_first_[i]];
+    // The box window reads F's input after the class conv has written its logits: the two must not share arena
+    // memory (the layout frees a buffer after its last op in program order, which for F's input is F unless the
+    // plan keeps it longer).  Whole buffers from their bases, both over images.
+    const OpRecord& c = prog_[gate_pairs_[i].cls];
+    const int64_t cb = c[34] > 0 ? c[36] : c[10], cst = c[34] > 0 ? c[38] : c[12];
+    if (f[1] < 0 || f[1] >= n_buffers || cb < 0 || cb >= n_buffers) continue;
+    const int64_t in_lo = offsets[f[1]], in_hi = in_lo + (int64_t)B * f[4] * f[5] * f[3] * 4;
+    const int64_t w_lo = offsets[cb], w_hi = w_lo + (int64_t)B * c[13] * c[14] * cst * 4;
+    if (f[1] == cb || (in_lo < w_hi && w_lo < in_hi)) continue;
+    bk.marks_off[i] = (int64_t)abytes;
+    abytes += align_up((size_t)B * head_mark_cells((int)f[13]) * head_mark_cells((int)f[14]) * sizeof(int), 256);
+  }
   // Every slot owns its arena, also when the slots are serialised on one stream (ARENA_CONCURRENT=0):
   // collect() of slot s may replay the classifier program for overflow crops after slot s+1's graph has
   // run, and that pass reads slot s's crop plan and activations.
@@ -527,6 +553,7 @@ void Executor::capture(Bucket& bk, int s) {
   if (s == 0) {
     bk.exec_order.clear();
     bk.gated.clear();
+    bk.launches.clear();
   }
   // One capture of ops [a, b) on the slot's stream.  The result D2H copy is issued after the graph launch, not
   // captured: a captured device->pinned-host memcpy node faulted on ROCm 7.0 (torch's runtime) while the same
@@ -540,6 +567,7 @@ void Executor::capture(Bucket& bk, int s) {
         bk.exec_order.push_back((int)(a + order[k]));
         if (gate[k] != nullptr) bk.gated.push_back((int)(a + order[k]));
       }
+      for (const Step& st : launch_plan(part, bk, (int)a, 0)) bk.launches.emplace_back((int)(a + st.pos), st.kind);
     }
     hipGraph_t g = nullptr;
     hipGraphExec_t ge = nullptr;
@@ -695,6 +723,42 @@ std::vector<size_t> Executor::exec_plan(const std::vector<OpRecord>& prog, const
   return order;
 }
 
+// Head split (head_marks.h): see launch_plan in executor.h.  F, the box conv and the class conv are adjacent ops, and
+// all five launches stay inside their three program slots.  The one lifetime the reordering stretches is that of F's
+// input, which the box window reads after the class conv has written: add_bucket checks that the two do not share
+// arena memory (marks_off stays -1 otherwise).  Everything that leaves a pair ungated leaves its F whole.
+std::vector<Executor::Step> Executor::launch_plan(const std::vector<OpRecord>& prog, const Bucket& bk, int op_offset,
+                                                  int force_impl) const {
+  std::vector<const HeadGatePair*> gate;
+  const std::vector<size_t> order = exec_plan(prog, bk, op_offset, force_impl, gate);
+  std::vector<Step> steps;
+  steps.reserve(order.size() + 6);
+  for (size_t k = 0; k < order.size(); ++k) steps.push_back(Step{order[k], LAUNCH_OP, gate[k]});
+  if (g_head_split == 0 || (g_head_split == 1 && bk.info.B < kHeadSplitMinBucket)) return steps;
+  for (size_t i = 0; i < gate_pairs_.size(); ++i) {
+    const HeadGatePair& gp = gate_pairs_[i];
+    const int fi = gate_first_[i];
+    const long lf = (long)fi - op_offset;
+    if (fi < 0 || lf < 0 || i >= bk.marks_off.size() || bk.marks_off[i] < 0) continue;
+    // the pair is gated in this slice: its box conv is the step after its class conv, F the step before that
+    size_t k = 0;
+    while (k < steps.size() && !(steps[k].kind == LAUNCH_OP && steps[k].gate == &gp)) ++k;
+    if (k >= steps.size() || k < 2 || steps[k - 2].pos != (size_t)lf || steps[k - 2].kind != LAUNCH_OP) continue;
+    if (prog[lf] != prog_[fi] || prog_[fi][30] != BATCH_IMAGES) continue;
+    const int f_impl = fi < (int)bk.impl.size() ? bk.impl[fi] : 0;
+    if (!(f_impl >= kF32X3HP && f_impl < kF32X3HP + kF32X3HPVariants)) continue;
+    int uh = 0, uw = 0;
+    if (gp.box >= (int)bk.impl.size() || !x3hg_pw_tile(bk.impl[gp.box], (int)prog_[gp.box][16], &uh, &uw)) continue;
+    if (uh % kMarkCell != 0 || uw % kMarkCell != 0) continue;
+    const size_t box_pos = steps[k].pos;
+    steps[k - 2].kind = LAUNCH_CLS_WINDOW;
+    steps[k - 2].gate = &gp;
+    const Step extra[2] = {Step{box_pos, LAUNCH_MARK, &gp}, Step{(size_t)lf, LAUNCH_BOX_WINDOW, &gp}};
+    steps.insert(steps.begin() + (long)k, extra, extra + 2);
+  }
+  return steps;
+}
+
 void Executor::enqueue_program(const std::vector<OpRecord>& prog, Bucket& bk, Slot& sl, hipStream_t s_main,
                                int op_offset, int force_impl) {
   Ctrl* ctrl = (Ctrl*)resolve(bk, sl, BUF_CTRL, 0, 1);
@@ -707,12 +771,29 @@ void Executor::enqueue_program(const std::vector<OpRecord>& prog, Bucket& bk, Sl
 
   // Lane ops (kLaneField) run in program order here: the lanes' side streams are driven by launch_graph() over
   // per-lane captured segments, not by forking inside one capture.
-  std::vector<const HeadGatePair*> gate;
-  const std::vector<size_t> order = exec_plan(prog, bk, op_offset, force_impl, gate);
-  for (size_t k = 0; k < prog.size(); ++k) {
-    const size_t oi = order[k];
+  const std::vector<Step> steps = launch_plan(prog, bk, op_offset, force_impl);
+  auto marks_of = [&](const HeadGatePair* gp) {
+    return (int*)(bk.d_arena[sl.idx] + bk.marks_off[(size_t)(gp - gate_pairs_.data())]);
+  };
+  for (const Step& step : steps) {
+    const size_t oi = step.pos;
     const OpRecord& r = prog[oi];
     hipStream_t s = s_main;
+    if (step.kind == LAUNCH_MARK) {  // r = the pair's box conv: the level's class logits follow its 1x1 output
+      HeadMarkParams m{};
+      m.n_levels = 1;
+      m.logits[0] = (const float*)resolve(bk, sl, r[36], r[37] + kHeadBoxChannels, 4);
+      m.H[0] = (int)r[13];
+      m.W[0] = (int)r[14];
+      m.ps[0] = (int)r[38];
+      m.marks[0] = marks_of(step.gate);
+      m.n = kHeadClsChannels;
+      head_gate_min(step.gate->conf_thr, &m.gate_min);
+      m.B = batch(r[30]);
+      m.bdev = bdev(r[30]);
+      head_mark(m, s);
+      continue;
+    }
     // field 47: activation precision of the op (0 bf16, 1 exact fp32; planner.OP_DTYPE_FIELD)
     const bool f32 = r[kDtypeField] == 1;
     const int eb = f32 ? 4 : 2;
@@ -771,11 +852,24 @@ void Executor::enqueue_program(const std::vector<OpRecord>& prog, Bucket& bk, Sl
           p.pw_ys = (int)r[38];
           p.pw_act = (int)r[39];
           if (!f32) p.impl = 2;  // bf16: the v3 halo-tile kernel; fp32: the tuned x3hg-pw variant
-          if (gate[k] != nullptr) {  // box conv of a head-gate pair: the level's class logits, already enqueued
+          if (step.gate != nullptr) {  // box conv of a head-gate pair: the level's class logits, already enqueued
             p.gate = (const float*)resolve(bk, sl, r[36], r[37] + kHeadBoxChannels, eb);
             p.gate_n = kHeadClsChannels;
-            head_gate_min(gate[k]->conf_thr, &p.gate_min);
+            head_gate_min(step.gate->conf_thr, &p.gate_min);
           }
+        }
+        if (step.kind == LAUNCH_CLS_WINDOW || step.kind == LAUNCH_BOX_WINDOW) {  // a split first head conv
+          const bool box = step.kind == LAUNCH_BOX_WINDOW;
+          p.n_lo = box ? 0 : kHeadBoxChannels;
+          p.n_hi = box ? kHeadBoxChannels : kHeadBoxChannels + kHeadClsChannels;
+          if (box) {
+            p.marks = marks_of(step.gate);
+            p.mark_halo = 1;  // the box conv is 3x3
+            x3hg_pw_tile(bk.impl[step.gate->box], (int)prog_[step.gate->box][16], &p.mark_uh, &p.mark_uw);
+          }
+          if (!conv_x3hp(p, s, box ? kHeadSplitBoxVariant : kHeadSplitClsVariant))
+            throw std::runtime_error("executor: the split first head conv does not fit its x3hp window kernel");
+          break;
         }
         if (f32)
           conv2d_f32(p, s);

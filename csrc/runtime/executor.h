@@ -36,6 +36,7 @@
 
 #include "../kernels/launch.h"
 #include "head_gate.h"
+#include "head_marks.h"
 #include "instance.h"
 
 namespace arena {
@@ -57,6 +58,21 @@ using OpRecord = std::array<int64_t, kOpFields>;
 // captured: a change applies to buckets added after it.
 void set_head_gate(bool v);
 bool get_head_gate();
+// ARENA_HEAD_SPLIT (default 1): a gated pair's first head conv runs as two channel windows, the class window before
+// the class conv and the box window after it, on the tiles a continuing box tile reads (head_marks.h).  0: off (the
+// launch sequence of the head gate alone); 1: in buckets of at least kHeadSplitMinBucket images; 2: in every bucket
+// (traces of the small buckets).  Read when a bucket is captured, as ARENA_HEAD_GATE is.
+void set_head_split(int v);
+int get_head_split();
+// The smallest traced bucket in which the split gains beyond the run-to-run drift (profiles/r11_head_split): below
+// it the two extra launches cost more than the skipped tiles give back.
+constexpr int kHeadSplitMinBucket = 32;
+// x3hp variants (halo_x3p.hip HP_VARIANTS) of the two windows: <4, 8, 3> = 8 x 16 px x 64 channels for the box
+// window, <5, 8, 1> = 8 x 16 px x 80 channels on per-tap stages for the class window (<5, 8, 3> needs 89 KB of LDS:
+// one workgroup per CU).  Stand-alone timings of the candidates: profiles/r11_head_split/README.md
+constexpr int kHeadSplitBoxVariant = 2, kHeadSplitClsVariant = 9;
+// One kernel launch of a captured program: the whole op, or a part of a split first head conv
+enum LaunchKind : int { LAUNCH_OP = 0, LAUNCH_CLS_WINDOW = 1, LAUNCH_BOX_WINDOW = 2, LAUNCH_MARK = 3 };
 
 enum OpType : int64_t {
   OP_CONV = 1,
@@ -253,6 +269,16 @@ class Executor : public BatchInstance {
     // the captured graphs' kernels in launch order, as indices into prog_ (program order except for the swapped
     // head-gate pairs), and the ops that run with a tile gate
     std::vector<int> exec_order, gated;
+    // every launch of the captured graphs in order: (op of prog_, LaunchKind); LAUNCH_MARK carries its box conv's op
+    std::vector<std::pair<int, int>> launches;
+    // head split: byte offset in each slot's arena allocation of the marks of gate_pairs_[i], -1 = that pair has
+    // no first conv to split
+    std::vector<int64_t> marks_off;
+  };
+  struct Step {
+    size_t pos;                  // position in the enqueued slice of prog_
+    int kind;                    // LaunchKind
+    const HeadGatePair* gate;    // LAUNCH_OP: the pair whose box conv this is, when gated; windows / marks: their pair
   };
 
   void alloc_slots();
@@ -275,6 +301,11 @@ class Executor : public BatchInstance {
   // not null, is the head-gate pair whose box conv is enqueued k-th
   std::vector<size_t> exec_plan(const std::vector<OpRecord>& prog, const Bucket& bk, int op_offset, int force_impl,
                                 std::vector<const HeadGatePair*>& gate) const;
+  // exec_plan as launches: a gated pair whose first conv F can be split (head_gate_first_conv, F in this slice and
+  // tuned to an x3hp variant, the box conv on an x3hg fused-1x1 tile of whole cells, the bucket large enough for
+  // g_head_split) becomes F's class window, the class conv, the level's marks, F's box window, the box conv
+  std::vector<Step> launch_plan(const std::vector<OpRecord>& prog, const Bucket& bk, int op_offset,
+                                int force_impl) const;
 
  public:
   // ops of prog_ in the order bucket B's graphs run them, and those among them that run with a tile gate
@@ -285,6 +316,11 @@ class Executor : public BatchInstance {
   std::vector<int> gated_ops(int B) const {
     auto it = buckets_.find(B);
     return it == buckets_.end() ? std::vector<int>{} : it->second.gated;
+  }
+  // every kernel launch of bucket B's graphs in order, as (op, LaunchKind)
+  std::vector<std::pair<int, int>> launch_order(int B) const {
+    auto it = buckets_.find(B);
+    return it == buckets_.end() ? std::vector<std::pair<int, int>>{} : it->second.launches;
   }
   // conv kernel family per program op chosen for bucket B (0 = default / not a conv)
   std::vector<int> conv_choices(int B) const {
@@ -317,6 +353,7 @@ class Executor : public BatchInstance {
   size_t weights_bytes_ = 0;
   std::vector<OpRecord> prog_, cls_prog_;
   std::vector<HeadGatePair> gate_pairs_;  // head_gate_pairs(prog_)
+  std::vector<int> gate_first_;           // head_gate_first_conv of each pair, -1 = none
   std::map<int, Bucket> buckets_;
   Slot slots_[kMaxSlots];
   int n_slots_ = 2;

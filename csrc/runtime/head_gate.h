@@ -101,4 +101,36 @@ inline std::vector<HeadGatePair> head_gate_pairs(const int64_t* ops, int n, int 
   return out;
 }
 
+// The first head conv F of a pair, or -1: the op directly before the box conv, an fp32 3x3 stride-1 CONV with
+// kHeadBoxChannels + kHeadClsChannels output channels over the pair's map, without pointwise epilogue, residual or
+// second output, whose output range is exactly the box conv's input channels followed by the class conv's, and
+// which nothing but the pair reads (every op's input buffers: r[1] and the residual r[22] of a CONV, the three head
+// levels of DECODE / raw output, r[1] of every other op).  The box half of such a conv is read only by the box conv
+// (head_marks.h), so the executor may run F as two channel windows around the class conv, all three inside the
+// program slots F .. cls: the lifetimes the arena layout was made for still hold.
+constexpr int64_t kHgOpYoloRaw = 13;
+inline int head_gate_first_conv(const int64_t* ops, int n, int fields, const HeadGatePair& gp) {
+  if (ops == nullptr || fields <= kHgDtypeField || gp.box < 1 || gp.cls != gp.box + 1 || gp.cls >= n) return -1;
+  auto rec = [&](int i) { return ops + (size_t)i * fields; };
+  const int fi = gp.box - 1;
+  const int64_t *f = rec(fi), *a = rec(gp.box), *c = rec(gp.cls);
+  constexpr int kN = kHeadBoxChannels + kHeadClsChannels;
+  if (!(f[0] == kHgOpConv && f[kHgDtypeField] == 1 && f[17] == 3 && f[18] == 3 && f[19] == 1 && f[15] == kN &&
+        f[34] == 0 && f[22] < 0 && f[25] < 0 && f[10] >= 0))
+    return -1;
+  if (!(f[13] == a[4] && f[14] == a[5] && f[13] == a[13] && f[14] == a[14] && f[30] == a[30])) return -1;
+  if (!(a[1] == f[10] && a[2] == f[11] && a[6] == kHeadBoxChannels && a[3] == f[12])) return -1;
+  if (!(c[1] == f[10] && c[2] == f[11] + kHeadBoxChannels && c[6] == kHeadClsChannels && c[3] == f[12])) return -1;
+  const int64_t buf = f[10];
+  for (int i = 0; i < n; ++i) {
+    if (i == fi || i == gp.box || i == gp.cls) continue;
+    const int64_t* r = rec(i);
+    bool reads = r[1] == buf;
+    if (r[0] == kHgOpConv) reads |= r[22] == buf;
+    if (r[0] == kHgOpDecode || r[0] == kHgOpYoloRaw) reads |= r[5] == buf || r[9] == buf;
+    if (reads) return -1;
+  }
+  return fi;
+}
+
 }  // namespace arena

@@ -248,6 +248,11 @@ def plan_yolo(pb: ProgramBuilder, y: YOLOv5nu, T: int = 640, tensor_input: bool 
                     pw=(*fold_conv_bn(d.cv2[lvl][2], None), View(D, 0, 4 * d.reg_max), None))
             pb.conv(View(H1, c2, c3), View(BUF_NONE, 0, c3), *fold(d.cv3[lvl][1]),
                     pw=(*fold_conv_bn(d.cv3[lvl][2], None), View(D, 4 * d.reg_max, nc), None))
+            if pb.f32:
+                # head split (csrc/runtime/head_marks.h): the executor may run the box half of the first conv
+                # after the class conv, so the first conv's input must outlive the class conv's writes to D (the
+                # executor checks the two ranges and leaves the conv whole when they overlap)
+                P.last = max(P.last, len(pb.ops) - 1)
         else:
             pb.conv(View(H1, 0, c2), View(H2, 0, c2), *fold(d.cv2[lvl][1]))
             pb.conv(View(H1, c2, c3), View(H2, c2, c3), *fold(d.cv3[lvl][1]))

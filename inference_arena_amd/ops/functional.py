@@ -47,8 +47,13 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, stride: in
                 res: torch.Tensor | None = None, res_coff: int = 0, out2: torch.Tensor | None = None,
                 out2_coff: int = 0, f32out: bool = False, out_hw=None, bdev: torch.Tensor | None = None,
                 packed=None, impl: int = 0, pw=None, pw_out: torch.Tensor | None = None, pw_out_coff: int = 0,
-                gate=None) -> torch.Tensor:
+                gate=None, window=None, marks=None) -> torch.Tensor:
     """NHWC conv with fused bias/act/residual/upsampled copy.
+
+    ``window=(n_lo, n_hi)`` (x3hp kernels, impl 191 + v, only): compute and store only the output channels
+    [n_lo, n_hi); the rest of ``out`` keeps its contents.  ``marks=(m, uh, uw, halo)`` (x3hp only): int32 ``m``
+    [B, ceil(Ho / 8), ceil(Wo / 8)] cell marks (``head_mark``); an output tile that no continuing ``uh`` x ``uw``
+    consumer tile grown by ``halo`` pixels reads is skipped and keeps its contents (ConvParams.marks).
 
     ``pw=(w2, b2)`` (fp32 3x3 stride-1 only): the Detect-head 1x1 ``w2`` [C2, Cout, 1, 1] is applied to the
     activated result inside the x3hg epilogue (impl 145 + v) and only its [B, Ho, Wo, C2] output is returned;
@@ -112,6 +117,14 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, stride: in
             pwd.update({"gate": _ptr(gt, gcoff), "gate_n": int(gn), "gate_min": float(gmin)})
     elif gate is not None or pw_out is not None:
         raise ValueError("conv2d_nhwc: gate / pw_out need pw")
+    if window is not None:
+        pwd.update({"n_lo": int(window[0]), "n_hi": int(window[1])})
+    if marks is not None:
+        mt, uh, uw, halo = marks
+        if (mt.dtype != torch.int32 or mt.device != x.device or not mt.is_contiguous()
+                or tuple(mt.shape) != (B, (Ho + 7) // 8, (Wo + 7) // 8)):
+            raise ValueError("conv2d_nhwc: marks must be contiguous int32 [B, ceil(Ho / 8), ceil(Wo / 8)]")
+        pwd.update({"marks": _ptr(mt), "mark_uh": int(uh), "mark_uw": int(uw), "mark_halo": int(halo)})
     skd = {}
     if 171 <= int(impl) < 180:  # split-K x3g: a workspace for the partial tiles (splits <= 8)
         ws = torch.empty(8 * B * Ho * Wo * cpad, dtype=torch.float32, device=x.device)
@@ -129,6 +142,31 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, stride: in
     if pw is not None:
         torch.cuda.synchronize(x.device)  # keep the packed 1x1 weights alive until the kernel ran
     return out
+
+
+def head_mark(logits: torch.Tensor, coff: int, n: int, gate_min: float, marks: torch.Tensor | None = None,
+              bdev: torch.Tensor | None = None, levels=None) -> torch.Tensor | list:
+    """Detect-head cell marks (csrc/kernels/head_mark.hip): int32 [B, ceil(H / 8), ceil(W / 8)], 1 iff one of
+    ``logits[b, y, x, coff:coff + n]`` (float32 [B, H, W, C]) of an in-map pixel of the 8 x 8 cell is >= gate_min.
+    Cells of images at or past the live count (``bdev``) keep the contents of ``marks``.  ``levels``: further
+    (logits, marks) pairs marked by the same launch; the result is then the list of all mark tensors."""
+    lv = [(logits, marks)] + list(levels or [])
+    out = []
+    for lg, mk in lv:
+        B, H, W, C = lg.shape
+        if lg.dtype != torch.float32 or not lg.is_contiguous() or coff < 0 or coff + n > C:
+            raise ValueError("head_mark: logits must be contiguous float32 [B, H, W, >= coff + n]")
+        if mk is None:
+            mk = torch.zeros(B, (H + 7) // 8, (W + 7) // 8, dtype=torch.int32, device=lg.device)
+        if (mk.dtype != torch.int32 or mk.device != lg.device or not mk.is_contiguous()
+                or tuple(mk.shape) != (B, (H + 7) // 8, (W + 7) // 8) or B != lv[0][0].shape[0]):
+            raise ValueError("head_mark: marks must be contiguous int32 [B, ceil(H / 8), ceil(W / 8)]")
+        out.append(mk)
+    native().head_mark({"logits": [_ptr(lg, coff) for lg, _ in lv], "marks": [_ptr(mk) for mk in out],
+                        "H": [lg.shape[1] for lg, _ in lv], "W": [lg.shape[2] for lg, _ in lv],
+                        "ps": [lg.shape[3] for lg, _ in lv], "n": int(n), "gate_min": float(gate_min),
+                        "B": lv[0][0].shape[0], "bdev": _ptr(bdev), "stream": _stream()})
+    return out if levels else out[0]
 
 
 def dwconv3x3_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, stride: int = 1, act="relu6",

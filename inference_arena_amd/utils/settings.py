@@ -68,6 +68,9 @@ class Settings(BaseModel):
     ARENA_IR_S2K16: int = 1
     # likewise read natively: 1 the fp32 Detect head's box convs skip tiles without a passing class logit, 0 dense
     ARENA_HEAD_GATE: int = 1
+    # likewise: 1 a gated level's first head conv runs as a class window and a box window over the tiles a kept box
+    # tile reads (buckets >= 16), 0 whole and dense, 2 in every bucket
+    ARENA_HEAD_SPLIT: int = 1
 
     @classmethod
     def from_env(cls, env_file: str | Path = ".env", **overrides) -> "Settings":

@@ -52,13 +52,20 @@ def norm_name(name: str) -> str:
     return n.strip()
 
 
-def read_op_table(path: Path) -> tuple[dict[int, float], dict[int, str]]:
-    """analyze_trace.py markdown table -> ({op: mean us}, {op: kernel name})."""
+def read_op_table(path: Path) -> tuple[dict[tuple, float], dict[tuple, str]]:
+    """analyze_trace.py markdown table -> ({launch: mean us}, {launch: kernel name}); a launch is (op, kind), the
+    row label being the op index, followed by `` cls`` / `` box`` / `` marks`` for the parts of a split first head
+    conv (analyze_trace.LAUNCH_LABEL)."""
+    from tools.analyze_trace import LAUNCH_LABEL
+
+    kind_of = {v.strip(): k for k, v in LAUNCH_LABEL.items()}
     times, names = {}, {}
     for line in Path(path).read_text().splitlines():
         cells = [c.strip() for c in line.strip().strip("|").split("|")]
-        if len(cells) >= 7 and cells[0].isdigit():
-            k = int(cells[0])
+        label = cells[0].split() if cells else []
+        if len(cells) >= 7 and label and label[0].isdigit() and len(label) <= 2 and \
+                (label[1] if len(label) == 2 else "") in kind_of:
+            k = (int(label[0]), kind_of[label[1] if len(label) == 2 else ""])
             names[k] = cells[3]
             try:
                 times[k] = float(cells[6])
@@ -115,9 +122,13 @@ def find_replays(by_q: dict[str, list[dict]], expected: list[str], keep: int) ->
     return out[-keep:]
 
 
-def duration_check(vals: dict[int, dict[str, list[float]]], dur_pmc: dict[int, list[float]], times: dict[int, float],
-                   tol: float) -> tuple[list[str], dict[int, float]]:
-    """GRBM-derived duration of each op's counted dispatches against the op table: (problems, {op: us_grbm})."""
+def duration_check(vals: dict[tuple, dict[str, list[float]]], dur_pmc: dict[tuple, list[float]],
+                   times: dict[tuple, float], tol: float) -> tuple[list[str], dict[tuple, float]]:
+    """GRBM-derived duration of each op's counted dispatches against the op table: (problems, {op: us_grbm}).  Keys are ops or (op, launch kind) pairs."""
+    from tools.analyze_trace import LAUNCH_LABEL
+
+    def label(k) -> str:
+        return f"{k[0]}{LAUNCH_LABEL[k[1]]}" if isinstance(k, tuple) else str(k)
     samples = [(statistics.median(vals[k]["GRBM_GUI_ACTIVE"]) / 8.0, statistics.median(dur_pmc[k]))
                for k in vals if "GRBM_GUI_ACTIVE" in vals[k] and dur_pmc.get(k)]
     long_ = [c / us for c, us in samples if us >= 30.0]
@@ -135,14 +146,14 @@ def duration_check(vals: dict[int, dict[str, list[float]]], dur_pmc: dict[int, l
             continue
         got = us_grbm[k] - floor
         if abs(got - times[k]) > tol * times[k] + 2.0:
-            bad.append(f"op {k}: counted {got:.1f} us (after the {floor:.1f} us floor) vs {times[k]:.1f} us traced")
+            bad.append(f"op {label(k)}: counted {got:.1f} us (after the {floor:.1f} us floor) vs {times[k]:.1f} us traced")
     return bad, us_grbm
 
 
 def main(argv=None) -> int:
     from inference_arena_amd.engine.plans import plan_pipeline
     from inference_arena_amd.models.zoo import default_models
-    from tools.analyze_trace import KIND, describe, load_order
+    from tools.analyze_trace import KIND, LAUNCH_LABEL, describe, load_order
 
     ap = argparse.ArgumentParser()
     ap.add_argument("csvs", nargs="+")
@@ -161,13 +172,13 @@ def main(argv=None) -> int:
     times, tnames = read_op_table(Path(a.times))
     prog = plan_pipeline(*default_models(0), conf_thr=0.5, iou_thr=0.45, dtype=a.dtype)
     n_ops = prog.ops.shape[0]
-    if sorted(tnames) != list(range(n_ops)):
-        print(f"op table lists ops {min(tnames, default=-1)}..{max(tnames, default=-1)}, program has {n_ops}",
-              file=sys.stderr)
+    order = load_order(a.order, n_ops)  # (op, kind) per launch of a replay
+    if sorted(tnames) != sorted(order):
+        print(f"op table lists {len(tnames)} launches of ops {min(tnames, default=(-1,))[0]}.."
+              f"{max(tnames, default=(-1,))[0]}, the executed order has {len(order)} over {n_ops} ops", file=sys.stderr)
         return 2
-    order = load_order(a.order, n_ops)
-    expected = [tnames[k] for k in range(n_ops)]
-    expected_run = [tnames[order[pos]] for pos in range(n_ops)]  # kernel names in launch order
+    expected = tnames
+    expected_run = [tnames[k] for k in order]  # kernel names in launch order
     problems = []
     vals: dict[int, dict[str, list[float]]] = defaultdict(lambda: defaultdict(list))
     per_set = []
@@ -193,7 +204,7 @@ def main(argv=None) -> int:
     lines = ["| op | kind | shape | kernel | " + " | ".join(counters)
              + " | valu/mfma | lds/mfma | conflict % | mfma busy % | wait % | HBM MB (rd+wr) | us | TB/s |",
              "|" + "---|" * (4 + len(counters) + 8)]
-    for k in range(n_ops):
+    for k in sorted(order):
         if k not in vals:
             continue
         m = {c: sum(v) / len(v) for c, v in vals[k].items()}
@@ -213,8 +224,9 @@ def main(argv=None) -> int:
         hb = f"{mbytes:.1f}" if ("FETCH_SIZE" in m or "WRITE_SIZE" in m) else "-"
         us = times.get(k)
         tbs = f"{mbytes * 1e6 / (us * 1e-6) / 1e12:.2f}" if us and hb != "-" else "-"
-        kind = KIND.get(int(prog.ops[k][0]), "?")
-        lines.append(f"| {k} | {kind} | {describe(prog.ops[k])} | {expected[k]} | "
+        kind = "marks" if k[1] == 3 else KIND.get(int(prog.ops[k[0]][0]), "?")
+        shape = "" if k[1] == 3 else describe(prog.ops[k[0]])
+        lines.append(f"| {k[0]}{LAUNCH_LABEL[k[1]]} | {kind} | {shape} | {expected[k]} | "
                      + " | ".join(f"{m[c]:.3g}" if c in m else "-" for c in counters)
                      + f" | {vr} | {lr} | {cf} | {mb} | {wt} | {hb} | {us if us else '-'} | {tbs} |")
     lines.append("")

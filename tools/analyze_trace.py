@@ -5,7 +5,10 @@ The executor's hipGraph replays the program's ops one kernel per op, in
 program order except for the Detect head's gated pairs, whose class conv runs
 before its box conv: the k-th arena kernel of each replay is op ``order[k]``,
 ``order`` being the executed order the executor reports (``--order``, written
-by tools/profile_engine.py ``--order-out``; without it, program order).  This tool takes the last
+by tools/profile_engine.py ``--order-out``; without it, program order).  Where the executor splits a first head
+conv, the order file also lists every launch (``launches``: the conv's class window, its box window and the cell
+marks are kernels of their own) and each gets a row of its own, labelled ``47 cls``, ``47 box``, ``48 marks``.
+This tool takes the last
 ``--replays`` complete replays from ``*_kernel_trace.csv``, averages each op's
 duration and prints a per-op table (op index, kind, layer shape, kernel
 variant, VGPRs, grid, mean us, share) plus per-kind totals.
@@ -61,16 +64,25 @@ def first_kernel(op0) -> str:
     return first
 
 
-def load_order(path, n_ops: int) -> list[int]:
-    """Executed order (tools/profile_engine.py --order-out): position in a replay -> program op; None: program order."""
+LAUNCH_LABEL = {0: "", 1: " cls", 2: " box", 3: " marks"}  # executor.h LaunchKind
+
+
+def load_order(path, n_ops: int) -> list[tuple[int, int]]:
+    """Executed launches (tools/profile_engine.py --order-out): position in a replay -> (program op, launch kind);
+    None: program order.  Kind 0 is the whole op, 1 / 2 the class / box window of a split first head conv, 3 the
+    cell marks launched before that op's box conv."""
     if not path:
-        return list(range(n_ops))
+        return [(k, 0) for k in range(n_ops)]
     import json
 
-    order = [int(v) for v in json.loads(Path(path).read_text())["exec_order"]]
+    d = json.loads(Path(path).read_text())
+    order = [int(v) for v in d["exec_order"]]
     if sorted(order) != list(range(n_ops)):
         raise SystemExit(f"{path}: not a permutation of the program's {n_ops} ops")
-    return order
+    launches = [(int(op), int(kind)) for op, kind in d.get("launches") or [(op, 0) for op in order]]
+    if [op for op, kind in launches if kind in (0, 1)] != order:
+        raise SystemExit(f"{path}: the launches do not visit the ops in the executed order")
+    return launches
 
 
 def merge_split_k(q: list[dict]) -> list[dict]:
@@ -105,7 +117,8 @@ def main(argv=None) -> int:
     prog = plan_pipeline(*default_models(a.seed), conf_thr=0.5, iou_thr=0.45, dtype=a.dtype)
     n_ops = prog.ops.shape[0]
     order = load_order(a.order, n_ops)
-    pos_of = {op: k for k, op in enumerate(order)}
+    pos_of = {launch: k for k, launch in enumerate(order)}
+    n_ops = len(order)  # kernels per replay from here on
     rows = [r for r in csv.DictReader(open(a.trace)) if "arena::" in r["Kernel_Name"]]
     # the executor runs each staging slot on its own stream: slice replays per hardware queue so that
     # kernels of concurrently running graphs are not interleaved
@@ -113,7 +126,7 @@ def main(argv=None) -> int:
     by_q = defaultdict(list)
     for r in rows:
         by_q[r[qkey] if qkey else 0].append(r)
-    first = first_kernel(prog.ops[order[0]])
+    first = first_kernel(prog.ops[order[0][0]])
     replays = []
     for qk in list(by_q):
         by_q[qk] = merge_split_k(sorted(by_q[qk], key=lambda r: int(r["Start_Timestamp"])))
@@ -123,7 +136,7 @@ def main(argv=None) -> int:
     replays = [rp for rp in replays if len(rp) == n_ops]
     # a program with several stamp ops starts a window at each of them, and overflow classification passes put
     # further kernels between replays: keep the windows whose stamp kernels sit exactly at the program's stamp ops
-    is_stamp = [int(prog.ops[order[pos]][0]) == 18 for pos in range(n_ops)]
+    is_stamp = [int(prog.ops[order[pos][0]][0]) == 18 for pos in range(n_ops)]
     replays = [rp for rp in replays if [("stamp_kernel" in r["Kernel_Name"]) for r in rp] == is_stamp]
     replays.sort(key=lambda rp: int(rp[0]["Start_Timestamp"]))
     # keep replays whose kernel sequence matches the program's final one (drops slices that straddle
@@ -144,15 +157,16 @@ def main(argv=None) -> int:
     total = sum(med.values())
     lines = ["| op | kind | shape | kernel | vgpr | grid | mean us | share |", "|---|---|---|---|---|---|---|---|"]
     per_kind = defaultdict(float)
-    for k in range(n_ops):
+    for k in sorted(order):
         r = replays[-1][pos_of[k]]
         us = med[k]
-        kind = KIND.get(int(prog.ops[k][0]), "?")
+        kind = "marks" if k[1] == 3 else KIND.get(int(prog.ops[k[0]][0]), "?")
         per_kind[kind] += us
         name = r["Kernel_Name"].replace("void arena::", "").replace("arena::", "").split("(")[0]
         grid = f"{int(r['Grid_Size_X']) // max(1, int(r['Workgroup_Size_X']))}x{r['Grid_Size_Y']}"
-        lines.append(f"| {k} | {kind} | {describe(prog.ops[k])} | {name} | {r['VGPR_Count']}+{r['Accum_VGPR_Count']} "
-                     f"| {grid} | {us:.1f} | {100 * us / total:.1f}% |")
+        shape = "" if k[1] == 3 else describe(prog.ops[k[0]])
+        lines.append(f"| {k[0]}{LAUNCH_LABEL[k[1]]} | {kind} | {shape} | {name} "
+                     f"| {r['VGPR_Count']}+{r['Accum_VGPR_Count']} | {grid} | {us:.1f} | {100 * us / total:.1f}% |")
     lines.append("")
     lines.append(f"replays: {len(replays)} (per-op medians); device time per replay: {total:.1f} us")
     lines.append("")

@@ -34,6 +34,7 @@ SOURCES = [
     "kernels/gemm_x3.hip",
     "kernels/halo_x3g.hip",
     "kernels/halo_x3p.hip",
+    "kernels/head_mark.hip",
     "kernels/stem_x3.hip",
     "kernels/ir_f32.hip",
     "kernels/ir_crop_f32.hip",

@@ -2,7 +2,8 @@
 """Engine-only driver for rocprofv3: runs ``--batches`` full batches of the curated workload through
 one GpuPipeline (``--dtype``), sequentially, so a kernel trace maps one graph replay per batch onto
 the program's ops (tools/analyze_trace.py).  ``--order-out`` writes the order in which the bucket's graphs launch
-the program's ops (the executor swaps the Detect head's gated pairs) for the analysis tools' ``--order``."""
+the program's ops (the executor swaps the Detect head's gated pairs) and every kernel launch of a replay (a split
+first head conv is two windows and a mark kernel) for the analysis tools' ``--order``."""
 from __future__ import annotations
 
 import argparse
@@ -26,7 +27,7 @@ def main(argv=None) -> int:
                     help="detector confidence threshold (default: the configured one); a program the tuning table "
                          "does not hold is tuned by timing unless ARENA_TUNING=off")
     ap.add_argument("--order-out", default=None,
-                    help="write {bucket, exec_order, gated} as JSON here (put it next to the trace)")
+                    help="write {bucket, exec_order, gated, launches} as JSON here (put it next to the trace)")
     a = ap.parse_args(argv)
     import json
 
@@ -47,7 +48,10 @@ def main(argv=None) -> int:
         order = list(pipe.ex.exec_order(B)) if hasattr(pipe.ex, "exec_order") else list(range(n_ops))
         gated = list(pipe.ex.gated_ops(B)) if hasattr(pipe.ex, "gated_ops") else []
         Path(a.order_out).parent.mkdir(parents=True, exist_ok=True)
-        Path(a.order_out).write_text(json.dumps({"bucket": B, "exec_order": order, "gated": gated}) + "\n")
+        launches = [list(x) for x in pipe.ex.launch_order(B)] if hasattr(pipe.ex, "launch_order") \
+            else [[op, 0] for op in order]
+        Path(a.order_out).write_text(json.dumps({"bucket": B, "exec_order": order, "gated": gated,
+                                                 "launches": launches}) + "\n")
     if a.inputs == "jpeg":
         from inference_arena_amd.data.synthetic import encode_jpeg
         from inference_arena_amd.ops import native
