@@ -1007,6 +1007,8 @@ PYBIND11_MODULE(_C, m) {
              c.threads = get<int>(cfg, "threads", c.threads);
              c.jpeg_device = get<bool>(cfg, "jpeg_device", c.jpeg_device);
              c.max_image_pixels = get<int64_t>(cfg, "max_image_pixels", c.max_image_pixels);
+             if (cfg.contains("progressive") && !cfg["progressive"].is_none())  // absent: the process default
+               c.progressive = cfg["progressive"].cast<bool>() ? 1 : 0;
              c.buffer_cap = get<int64_t>(cfg, "buffer_cap", c.buffer_cap);
              int ndev = 0;
              const bool gpu = hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
@@ -1055,6 +1057,7 @@ PYBIND11_MODULE(_C, m) {
              d["native"] = s.native;
              d["fallback"] = s.fallback;
              d["errors"] = s.errors;
+             d["progressive_decoded"] = s.progressive_decoded;
              d["cpu_decode_ms"] = s.cpu_decode_ms;
              return d;
            })
@@ -1245,6 +1248,8 @@ PYBIND11_MODULE(_C, m) {
              c.decode_threads = get<int>(cfg, "decode_threads", c.decode_threads);
              c.jpeg_device = get<bool>(cfg, "jpeg_device", c.jpeg_device);
              c.max_image_pixels = get<int64_t>(cfg, "max_image_pixels", c.max_image_pixels);
+             if (cfg.contains("progressive") && !cfg["progressive"].is_none())  // absent: the process default
+               c.progressive = cfg["progressive"].cast<bool>() ? 1 : 0;
              c.decode_buffer_cap = get<int64_t>(cfg, "decode_buffer_cap", c.decode_buffer_cap);
              c.kserve_model = get<std::string>(cfg, "kserve_model", c.kserve_model);
              // decoded uploads live in pinned memory when a GPU is present (the executor DMAs from them)
@@ -1334,6 +1339,7 @@ PYBIND11_MODULE(_C, m) {
              d["native_decoded"] = s.native_decoded;
              d["fallback_decoded"] = s.fallback_decoded;
              d["oriented_decoded"] = s.oriented_decoded;
+             d["progressive_decoded"] = s.progressive_decoded;
              d["bodies_recycled"] = s.bodies_recycled;
              d["bodies_allocated"] = s.bodies_allocated;
              d["cpu_parse_ms"] = s.cpu_parse_ms;

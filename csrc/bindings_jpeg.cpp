@@ -43,6 +43,7 @@ py::dict info_dict(const JpegInfo& in) {
   d["mcux"] = in.mcux;
   d["mcuy"] = in.mcuy;
   d["restart_interval"] = in.restart_interval;
+  d["progressive"] = in.progressive;
   d["coef_count"] = in.coef_count;
   py::list comps;
   for (int c = 0; c < in.ncomp; ++c) {
@@ -66,9 +67,12 @@ struct Parsed {
   std::vector<int16_t> coef;
 };
 
-JpegStatus parse_decode(const std::string& data, Parsed& p, std::string& err, int64_t max_pixels) {
+// progressive: None = the process default (jpeg_progressive_enabled), else the per-call switch of jpeg_parse
+int progressive_arg(const py::object& o) { return o.is_none() ? -1 : (o.cast<bool>() ? 1 : 0); }
+
+JpegStatus parse_decode(const std::string& data, Parsed& p, std::string& err, int64_t max_pixels, int progressive) {
   const uint8_t* b = (const uint8_t*)data.data();
-  JpegStatus st = jpeg_parse(b, data.size(), p.info, err, max_pixels);
+  JpegStatus st = jpeg_parse(b, data.size(), p.info, err, max_pixels, progressive);
   if (st != JpegStatus::Ok) return st;
   p.coef.assign((size_t)p.info.coef_count, 0);
   return jpeg_decode_coefs(b, data.size(), p.info, p.coef.data(), err);
@@ -170,18 +174,41 @@ py::dict encode_device(const U8Array& frame, const py::object& boxes, int device
 void bind_jpeg(py::module& m) {
   m.attr("SIZEOF_JPEG_DESC") = (int)sizeof(JpegDesc);
 
+  m.def("jpeg_progressive_default", &jpeg_progressive_enabled,
+        "Process default of the progressive switch (ARENA_JPEG_PROGRESSIVE, default 0): what progressive=None means.");
+  m.def("set_jpeg_progressive_default", &jpeg_set_progressive_enabled, py::arg("on"),
+        "Replace the process default of the progressive switch; returns the previous value.  Executor.run on encoded\n"
+        "bytes and every config without a \"progressive\" key follow it.");
+
   m.def(
       "jpeg_coefs",
-      [](py::bytes data, int64_t max_pixels) {
+      [](py::bytes data, int64_t max_pixels, py::object progressive, bool compact) {
         std::string s = data;
         Parsed p;
         std::string err;
         JpegStatus st;
+        const int prog = progressive_arg(progressive);
+        bool fits = true;
         {
           py::gil_scoped_release nogil;
-          st = parse_decode(s, p, err, max_pixels);
+          if (!compact) {
+            st = parse_decode(s, p, err, max_pixels, prog);
+          } else {  // through the serving paths' payload: jpeg_decode_compact, expanded again
+            st = jpeg_parse((const uint8_t*)s.data(), s.size(), p.info, err, max_pixels, prog);
+            if (st == JpegStatus::Ok) {
+              std::vector<uint8_t> payload((size_t)jpeg_compact_capacity(p.info));
+              st = jpeg_decode_compact((const uint8_t*)s.data(), s.size(), p.info, payload.data(), err);
+              if (st == JpegStatus::Ok) {
+                fits = p.info.compact_bytes <= (int64_t)payload.size();
+                p.coef.assign((size_t)p.info.coef_count, 0);
+                jpeg_compact_to_dense(p.info, payload.data(), p.coef.data());
+              }
+            }
+          }
         }
+        if (!fits) throw std::runtime_error("jpeg_coefs: the compact payload exceeds jpeg_compact_capacity");
         py::dict out = info_dict(p.info);
+        if (compact) out["compact_bytes"] = p.info.compact_bytes;
         out["status"] = status_name(st);
         out["error"] = err;
         py::array_t<int16_t> a((py::ssize_t)p.coef.size());
@@ -189,20 +216,23 @@ void bind_jpeg(py::module& m) {
         out["coef"] = a;
         return out;
       },
-      py::arg("data"), py::arg("max_pixels") = 0,
-      "Host entropy decode: dict(status, error, geometry, comps, coef=int16 natural-order blocks).");
+      py::arg("data"), py::arg("max_pixels") = 0, py::arg("progressive") = py::none(), py::arg("compact") = false,
+      "Host entropy decode: dict(status, error, geometry, comps, coef=int16 natural-order blocks).  progressive:\n"
+      "accept SOF2 files (None = the process default, ARENA_JPEG_PROGRESSIVE).  compact=True decodes into the\n"
+      "compact payload and expands it (adds compact_bytes).");
 
   m.def(
       "jpeg_decode_host",
-      [](py::bytes data, int64_t max_pixels) -> py::object {
+      [](py::bytes data, int64_t max_pixels, py::object progressive) -> py::object {
         std::string s = data;
         Parsed p;
         std::string err;
         JpegStatus st;
         std::vector<uint8_t> rgb;
+        const int prog = progressive_arg(progressive);
         {
           py::gil_scoped_release nogil;
-          st = parse_decode(s, p, err, max_pixels);
+          st = parse_decode(s, p, err, max_pixels, prog);
           if (st == JpegStatus::Ok) {
             rgb.resize((size_t)p.info.width * p.info.height * 3);
             jpeg_coefs_to_rgb(p.info, p.coef.data(), rgb.data());
@@ -213,15 +243,17 @@ void bind_jpeg(py::module& m) {
         std::memcpy(a.mutable_data(), rgb.data(), rgb.size());
         return py::make_tuple("ok", std::string(), a);
       },
-      py::arg("data"), py::arg("max_pixels") = 0,
+      py::arg("data"), py::arg("max_pixels") = 0, py::arg("progressive") = py::none(),
       "Whole decode on the host with the device kernels' arithmetic: (status, error, HxWx3 uint8 in the EXIF\n"
-      "orientation, or None).");
+      "orientation, or None).  progressive: accept SOF2 files (None = the process default).");
 
   m.def(
       "jpeg_decode_device",
-      [](std::vector<py::bytes> uploads, int device, bool guard) {
+      [](std::vector<py::bytes> uploads, int device, bool guard, py::object progressive, bool compact) {
         const int n = (int)uploads.size();
+        const int prog = progressive_arg(progressive);
         std::vector<Parsed> ps(n);
+        std::vector<std::vector<uint8_t>> payload(n);  // compact=True: what the serving paths ship
         std::vector<JpegDesc> descs(n);
         int64_t off = 0, max_blocks = 0, max_pix = 0;
         bool oriented = false;
@@ -233,14 +265,26 @@ void bind_jpeg(py::module& m) {
         for (int i = 0; i < n; ++i) {
           std::string err;
           const std::string s = uploads[i];
-          if (parse_decode(s, ps[i], err, 0) != JpegStatus::Ok) throw std::invalid_argument("upload " + std::to_string(i) + ": " + err);
+          JpegStatus st;
+          if (!compact) {
+            st = parse_decode(s, ps[i], err, 0, prog);
+          } else {
+            st = jpeg_parse((const uint8_t*)s.data(), s.size(), ps[i].info, err, 0, prog);
+            if (st == JpegStatus::Ok) {
+              payload[i].resize((size_t)jpeg_compact_capacity(ps[i].info));
+              st = jpeg_decode_compact((const uint8_t*)s.data(), s.size(), ps[i].info, payload[i].data(), err);
+            }
+            if (st == JpegStatus::Ok && ps[i].info.compact_bytes > (int64_t)payload[i].size())
+              throw std::runtime_error("jpeg_decode_device: the compact payload exceeds jpeg_compact_capacity");
+          }
+          if (st != JpegStatus::Ok) throw std::invalid_argument("upload " + std::to_string(i) + ": " + err);
           const JpegInfo& in = ps[i].info;
           if (guard) off += kGuard;
           rgb_off[i] = off;
           off = align256(off + (int64_t)in.width * in.height * 3 + (guard ? kGuard : 0));
           oriented |= in.orientation > 1;
           coef_base[i] = off;
-          off = align256(off + in.coef_count * 2);
+          off = align256(off + jpeg_payload_bytes(in));
           descs[i] = jpeg_device_desc(in, coef_base[i], off, rgb_off[i]);
           off = align256(off + in.plane_bytes);
           max_blocks = std::max<int64_t>(max_blocks, descs[i].total_blocks);
@@ -257,7 +301,8 @@ void bind_jpeg(py::module& m) {
         try {
           check(hipMemset(pool, 0xCD, (size_t)off), "hipMemset");
           for (int i = 0; i < n; ++i)
-            check(hipMemcpy(pool + coef_base[i], ps[i].coef.data(), ps[i].coef.size() * 2, hipMemcpyHostToDevice), "H2D coef");
+            check(hipMemcpy(pool + coef_base[i], compact ? (const void*)payload[i].data() : (const void*)ps[i].coef.data(),
+                            (size_t)jpeg_payload_bytes(ps[i].info), hipMemcpyHostToDevice), "H2D coef");
           check(hipMemcpy(dd, descs.data(), sizeof(JpegDesc) * n, hipMemcpyHostToDevice), "H2D desc");
           if (guard)
             for (int i = 0; i < n; ++i) {
@@ -293,9 +338,12 @@ void bind_jpeg(py::module& m) {
         }
         return out;
       },
-      py::arg("uploads"), py::arg("device") = 0, py::arg("guard") = false,
+      py::arg("uploads"), py::arg("device") = 0, py::arg("guard") = false, py::arg("progressive") = py::none(),
+      py::arg("compact") = false,
       "Entropy-decode on the host, reconstruct on the GPU (jpeg_idct.hip): list of HxWx3 uint8 in the EXIF\n"
-      "orientation.  guard=True surrounds each RGB region with guard bytes and raises if the kernels touched them.");
+      "orientation.  guard=True surrounds each RGB region with guard bytes and raises if the kernels touched them.\n"
+      "progressive: accept SOF2 files (None = the process default).  compact=True ships the compact payload\n"
+      "(jpeg_decode_compact) instead of dense blocks.");
   // ---- crop encoder ----
   m.attr("SIZEOF_JPEG_ENC_DESC") = (int)sizeof(JpegEncDesc);
 

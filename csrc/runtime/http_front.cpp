@@ -1299,7 +1299,7 @@ void HttpFrontEnd::native_decode(DecodeTask& t) {
   const uint8_t* data = (const uint8_t*)t.body.data() + t.off;
   auto up = std::make_shared<NativeUpload>();
   std::string err;
-  JpegStatus st = jpeg_parse(data, t.len, up->info, err, cfg_.max_image_pixels);
+  JpegStatus st = jpeg_parse(data, t.len, up->info, err, cfg_.max_image_pixels, cfg_.progressive);
   if (st == JpegStatus::Unsupported) return pool_submit(t.conn, t.t0, t.body, t.off, t.len, t.kind);  // PIL fallback
   if (st == JpegStatus::Corrupt)
     return fail_request(t.conn, err.find("image too large") != std::string::npos ? 413 : 500, err, t.kind);
@@ -1342,12 +1342,17 @@ void HttpFrontEnd::native_decode(DecodeTask& t) {
     }
     if (coef.capacity() > ((size_t)16 << 20)) std::vector<int16_t>().swap(coef);  // do not pin a huge frame's
   }
+  if (st == JpegStatus::Unsupported) {  // a progressive file only its scans show to be outside the split decoder
+    up.reset();                         // its buffer back to the pool before the PIL decode takes a slot
+    return pool_submit(t.conn, t.t0, t.body, t.off, t.len, t.kind);
+  }
   if (st != JpegStatus::Ok) return fail_request(t.conn, 500, err, t.kind);
   const double decode_ms = ms_since(t.t_queued);
   {
     std::lock_guard<std::mutex> sl(stats_mu_);
     ++stats_.native_decoded;
     if (ji.orientation > 1) ++stats_.oriented_decoded;
+    if (ji.progressive) ++stats_.progressive_decoded;
     stats_.cpu_decode_ms += thread_cpu_ms() - c0;
   }
   {

@@ -18,7 +18,9 @@
 //        (runtime/host_pool.h) -> DynamicBatcher::enqueue_input, zero-copy; the
 //        executor DMAs the coefficients and reconstructs the frame on the GPU
 //        (kernels/jpeg_idct.hip).  Uploads the split decoder does not cover
-//        (progressive JPEG, PNG, ...) fall through to:
+//        (PNG, CMYK, ...; progressive JPEG unless FrontConfig.progressive or
+//        ARENA_JPEG_PROGRESSIVE is on, and then those whose progression only the
+//        entropy decode finds incomplete or inconsistent) fall through to:
 //     -> the PIL decode pool: the bytes go into a slot of the pool's shared memory
 //        and a 16-byte task record to the least-loaded decode worker (the spawned
 //        PIL processes of server/decode_pool.py)
@@ -96,6 +98,7 @@ struct FrontConfig {
   // (same arithmetic, RGB staged like a PIL decode) — for instances without the device half and for A/B runs.
   bool jpeg_device = true;
   int64_t max_image_pixels = 50000000;     // decode-bomb guard (processing/transforms.py max_image_pixels)
+  int progressive = -1;  // SOF2 uploads: 1 split-decoded, 0 to the PIL pool, -1 the process default (jpeg_parse)
   int64_t decode_buffer_cap = 2LL << 30;   // host buffers of decoded uploads in flight (HostBufferPool cap)
   HostBufferPool::AllocFn host_alloc;      // pinning allocator for those buffers (empty: plain memory)
   HostBufferPool::FreeFn host_free;
@@ -126,6 +129,7 @@ struct FrontStats {
   int64_t connections = 0, open_connections = 0, detections = 0, timeouts = 0;
   int64_t native_decoded = 0, fallback_decoded = 0;  // uploads decoded by the split decoder / the PIL pool
   int64_t oriented_decoded = 0;  // of native_decoded: uploads with an EXIF orientation other than 1
+  int64_t progressive_decoded = 0;  // of native_decoded: progressive (SOF2) uploads
   int64_t bodies_recycled = 0, bodies_allocated = 0;  // request bodies served by the body pool / newly grown
   double sum_total_ms = 0, sum_decode_ms = 0, sum_queue_ms = 0, sum_gpu_ms = 0;
   // host CPU time (thread CPU clock) of request stages, summed: HTTP + multipart parse on the I/O threads, the

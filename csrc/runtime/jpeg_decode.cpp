@@ -2,6 +2,7 @@
 #include "runtime/jpeg_decode.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -33,6 +34,28 @@ bool huff_lengths_valid(const uint8_t* bits) {
 }
 
 uint16_t be16(const uint8_t* p) { return (uint16_t)((p[0] << 8) | p[1]); }
+
+// The tables of one DHT segment into dc[4] / ac[4]; false for a malformed segment or an over-subscribed code.
+bool read_dht(const uint8_t* seg, size_t sl, JpegHuffSpec* dc, JpegHuffSpec* ac) {
+  size_t q = 0;
+  while (q < sl) {
+    const int tc = seg[q] >> 4, th = seg[q] & 15;
+    if (tc > 1 || th > 3 || q + 17 > sl) return false;
+    JpegHuffSpec& h = tc == 0 ? dc[th] : ac[th];
+    int count = 0;
+    h.bits[0] = 0;
+    for (int l = 1; l <= 16; ++l) {
+      h.bits[l] = seg[q + l];
+      count += h.bits[l];
+    }
+    if (count > 256 || q + 17 + count > sl || !huff_lengths_valid(h.bits)) return false;
+    std::memset(h.vals, 0, sizeof h.vals);
+    std::memcpy(h.vals, seg + q + 17, count);
+    h.present = true;
+    q += 17 + count;
+  }
+  return true;
+}
 
 constexpr int kFastBits = 11;
 constexpr int kEobRun = 127;  // ac_fast run of an EOB entry
@@ -324,7 +347,21 @@ int exif_orientation(const uint8_t* seg, size_t sl) {
 
 }  // namespace
 
-JpegStatus jpeg_parse(const uint8_t* data, size_t n, JpegInfo& info, std::string& err, int64_t max_pixels) {
+namespace {
+std::atomic<int>& progressive_default() {
+  static std::atomic<int> on{[] {
+    const char* e = std::getenv("ARENA_JPEG_PROGRESSIVE");
+    return e != nullptr && std::atoi(e) != 0 ? 1 : 0;
+  }()};
+  return on;
+}
+}  // namespace
+
+bool jpeg_progressive_enabled() { return progressive_default().load(std::memory_order_relaxed) != 0; }
+bool jpeg_set_progressive_enabled(bool on) { return progressive_default().exchange(on ? 1 : 0) != 0; }
+
+JpegStatus jpeg_parse(const uint8_t* data, size_t n, JpegInfo& info, std::string& err, int64_t max_pixels,
+                      int progressive) {
   info = JpegInfo{};
   if (n < 4 || data[0] != 0xFF || data[1] != 0xD8) {
     err = "not a JPEG stream";
@@ -360,7 +397,9 @@ JpegStatus jpeg_parse(const uint8_t* data, size_t n, JpegInfo& info, std::string
     const uint8_t* seg = data + pos + 2;
     const size_t sl = len - 2;
     pos += len;
-    if (m == 0xC0 || m == 0xC1) {
+    if (m == 0xC0 || m == 0xC1 ||
+        (m == 0xC2 && (progressive < 0 ? jpeg_progressive_enabled() : progressive != 0))) {
+      info.progressive = m == 0xC2;
       if (saw_sof || sl < 6) {
         err = "Failed to decode image: bad SOF";
         return JpegStatus::Corrupt;
@@ -405,28 +444,9 @@ JpegStatus jpeg_parse(const uint8_t* data, size_t n, JpegInfo& info, std::string
       err = "progressive, lossless or arithmetic-coded JPEG";
       return JpegStatus::Unsupported;
     } else if (m == 0xC4) {
-      size_t q = 0;
-      while (q < sl) {
-        const int tc = seg[q] >> 4, th = seg[q] & 15;
-        if (tc > 1 || th > 3 || q + 17 > sl) {
-          err = "Failed to decode image: bad DHT";
-          return JpegStatus::Corrupt;
-        }
-        JpegHuffSpec& h = tc == 0 ? info.dc[th] : info.ac[th];
-        int count = 0;
-        h.bits[0] = 0;
-        for (int l = 1; l <= 16; ++l) {
-          h.bits[l] = seg[q + l];
-          count += h.bits[l];
-        }
-        if (count > 256 || q + 17 + count > sl || !huff_lengths_valid(h.bits)) {
-          err = "Failed to decode image: bad DHT";
-          return JpegStatus::Corrupt;
-        }
-        std::memset(h.vals, 0, sizeof h.vals);
-        std::memcpy(h.vals, seg + q + 17, count);
-        h.present = true;
-        q += 17 + count;
+      if (!read_dht(seg, sl, info.dc, info.ac)) {
+        err = "Failed to decode image: bad DHT";
+        return JpegStatus::Corrupt;
       }
     } else if (m == 0xDB) {
       size_t q = 0;
@@ -467,6 +487,11 @@ JpegStatus jpeg_parse(const uint8_t* data, size_t n, JpegInfo& info, std::string
       if (!saw_sof) {
         err = "Failed to decode image: scan before frame header";
         return JpegStatus::Corrupt;
+      }
+      if (info.progressive) {  // the scans are walked by the decode functions (decode_progressive)
+        info.first_sos = pos - len;
+        info.scan_begin = pos;
+        break;
       }
       const int ns = sl >= 1 ? seg[0] : 0;
       if (ns != info.ncomp) {
@@ -602,9 +627,339 @@ struct TableCache {
     return &x.table;
   }
 };
+
+// ---- progressive files (SOF2, T.81 Annex G; the behaviour matched is libjpeg's jdphuff.c) -----------------------
+
+inline bool fits16(int v) { return v >= -32768 && v <= 32767; }
+
+JpegStatus hand_back(std::string& err, const char* why) {
+  err = std::string("progressive JPEG outside the split decoder: ") + why;
+  return JpegStatus::Unsupported;
+}
+
+// One Huffman symbol as BitReader::decode reads it, but -1 where no code matches (libjpeg warns and goes on with a
+// zero: not a result to vouch for).
+__attribute__((always_inline)) inline int prog_symbol(BitReader& br, const HuffTable& t) {
+  const uint32_t e = t.fast[br.buf >> (64 - kFastBits)];
+  if (e) {
+    br.skip((int)(e >> 8));
+    return (int)(e & 0xFF);
+  }
+  const uint32_t code16 = (uint32_t)(br.buf >> 48);
+  for (int l = kFastBits + 1; l <= 16; ++l) {
+    const int32_t c = (int32_t)(code16 >> (16 - l));
+    if (c <= t.maxcode[l]) {
+      br.skip(l);
+      return t.vals[(t.valoff[l] + c) & 0xFF];
+    }
+  }
+  return -1;
+}
+
+// What is left of the data loaded so far, zero fill not counted: a well-formed segment ends within its last byte.
+inline bool prog_leftover(const BitReader& br) { return br.bits - 8 * (br.zfill + br.pad) >= 8; }
+
+// One block of each of the four scan kinds.  They return false where libjpeg would warn or a value leaves int16:
+// the file is handed back.  Runs that a corrupt stream sends past coefficient 63 land on kNatural's guard entries,
+// as in libjpeg.
+inline bool prog_dc_first(BitReader& br, const HuffTable& t, int& pred, int al, int16_t* blk) {
+  br.need(32);
+  const int s = prog_symbol(br, t);
+  if (s) {
+    if (s < 0 || s > 15) return false;
+    pred += extend(br.get(s), s);
+    if (!fits16(pred)) return false;
+  }
+  const int v = pred * (1 << al);
+  if (!fits16(v)) return false;
+  blk[0] = (int16_t)v;
+  return true;
+}
+
+inline void prog_dc_refine(BitReader& br, int al, int16_t* blk) {
+  br.need(1);
+  if (br.get(1)) blk[0] = (int16_t)(blk[0] | (1 << al));
+}
+
+inline bool prog_ac_first(BitReader& br, const HuffTable& t, int ss, int se, int al, int& eobrun, int16_t* blk) {
+  if (eobrun > 0) {  // inside a run of blocks whose band is all zero
+    --eobrun;
+    return true;
+  }
+  for (int k = ss; k <= se; ++k) {
+    br.need(32);  // a code (<= 16 bits) and its magnitude or run-length bits (<= 15)
+    const int32_t f = t.ac_fast[br.buf >> (64 - kFastBits)];
+    if (f) {  // one lookup, as in decode_block: a coefficient, ZRL or EOB0 (a run of this block only)
+      br.skip(f & 0xFF);
+      const int r = (f >> 8) & 0xFF;
+      if (r == kEobRun) break;
+      k += r;
+      const int v = (f >> 16) * (1 << al);
+      if (!fits16(v)) return false;
+      if (v) blk[kNatural[k]] = (int16_t)v;  // ZRL's zero is not stored: a corrupt run may end in another band
+      continue;
+    }
+    const int rs = prog_symbol(br, t);
+    if (rs < 0) return false;
+    const int r = rs >> 4, s = rs & 15;
+    if (s) {
+      k += r;
+      const int v = extend(br.get(s), s) * (1 << al);
+      if (!fits16(v)) return false;
+      blk[kNatural[k]] = (int16_t)v;
+    } else if (r == 15) {
+      k += 15;  // ZRL
+    } else {    // EOBr: this block's band ends here and so do the next (1 << r) + bits - 1 blocks'
+      eobrun = 1 << r;
+      if (r) eobrun += (int)br.get(r);
+      --eobrun;
+      break;
+    }
+  }
+  return true;
+}
+
+// the correction bit of a coefficient that earlier scans made nonzero
+inline void prog_correct(BitReader& br, int16_t& c, int p1) {
+  br.need(1);
+  if (br.get(1) && (c & p1) == 0) c = (int16_t)(c >= 0 ? c + p1 : c - p1);
+}
+
+inline bool prog_ac_refine(BitReader& br, const HuffTable& t, int ss, int se, int al, int& eobrun, int16_t* blk) {
+  const int p1 = 1 << al;
+  int k = ss;
+  if (eobrun == 0) {
+    for (; k <= se; ++k) {
+      br.need(32);
+      const int rs = prog_symbol(br, t);
+      if (rs < 0) return false;
+      int r = rs >> 4, s = rs & 15;
+      if (s) {
+        if (s != 1) return false;  // a new coefficient has magnitude 1 at this bit (libjpeg warns)
+        s = br.get(1) ? p1 : -p1;
+      } else if (r != 15) {
+        eobrun = 1 << r;
+        if (r) eobrun += (int)br.get(r);
+        break;  // the rest of the band is handled as the first block of the run, below
+      }
+      // pass r still-zero coefficients (16 for ZRL), correcting every nonzero one on the way
+      do {
+        int16_t& c = blk[kNatural[k]];
+        if (c != 0) prog_correct(br, c, p1);
+        else if (--r < 0) break;
+        ++k;
+      } while (k <= se);
+      if (s) blk[kNatural[k]] = (int16_t)s;
+    }
+  }
+  if (eobrun > 0) {
+    for (; k <= se; ++k) {
+      int16_t& c = blk[kNatural[k]];
+      if (c != 0) prog_correct(br, c, p1);
+    }
+    --eobrun;
+  }
+  return true;
+}
+
+// All scans of a progressive file into dense blocks (contract in jpeg_decode.h, jpeg_decode_coefs).
+JpegStatus decode_progressive(const uint8_t* data, size_t n, const JpegInfo& info, int16_t* coef, std::string& err) {
+  thread_local std::unique_ptr<TableCache> cache;
+  if (!cache) cache.reset(new TableCache());
+  std::memset(coef, 0, (size_t)info.coef_count * sizeof(int16_t));
+  JpegHuffSpec dc[4], ac[4];  // DHT between scans redefines them
+  for (int i = 0; i < 4; ++i) {
+    dc[i] = info.dc[i];
+    ac[i] = info.ac[i];
+  }
+  int ri = info.restart_interval;
+  // successive-approximation bit each coefficient is down to: -1 = never sent
+  int8_t sent[kJpegMaxComp][64];
+  std::memset(sent, -1, sizeof sent);
+  const char* const kTruncated = "Failed to decode image: image file is truncated";
+  size_t pos = info.first_sos;
+  for (int nscan = 1;; ++nscan) {
+    if (nscan > kJpegMaxScans) return hand_back(err, "too many scans");
+    // ---- scan header (pos: its length field) ----
+    if (pos + 2 > n) {
+      err = "Failed to decode image: truncated marker";
+      return JpegStatus::Corrupt;
+    }
+    const size_t len = be16(data + pos);
+    if (len < 2 || pos + len > n) {
+      err = "Failed to decode image: truncated marker segment";
+      return JpegStatus::Corrupt;
+    }
+    const uint8_t* seg = data + pos + 2;
+    const size_t sl = len - 2;
+    const int ns = sl >= 1 ? seg[0] : 0;
+    if (ns < 1 || ns > info.ncomp) return hand_back(err, "scan component count");
+    if (sl < 1 + 2 * (size_t)ns + 3) {
+      err = "Failed to decode image: bad SOS";
+      return JpegStatus::Corrupt;
+    }
+    if (sl != 1 + 2 * (size_t)ns + 3) return hand_back(err, "SOS length");
+    int ci[kJpegMaxComp] = {}, td[kJpegMaxComp] = {}, ta[kJpegMaxComp] = {};
+    int mcu_blocks = 0;
+    for (int i = 0; i < ns; ++i) {
+      const int cs = seg[1 + 2 * i];
+      int c = i ? ci[i - 1] + 1 : 0;  // in the frame's order, none twice
+      while (c < info.ncomp && info.comp_id[c] != cs) ++c;
+      if (c >= info.ncomp) return hand_back(err, "scan component selector");
+      ci[i] = c;
+      td[i] = seg[2 + 2 * i] >> 4;
+      ta[i] = seg[2 + 2 * i] & 15;
+      mcu_blocks += info.comp[c].h * info.comp[c].v;
+    }
+    const uint8_t* sp = seg + 1 + 2 * ns;
+    const int ss = sp[0], se = sp[1], ah = sp[2] >> 4, al = sp[2] & 15;
+    // G.1.1.1.1
+    if (ss == 0 ? se != 0 : (ns != 1 || ss > se || se > 63)) return hand_back(err, "spectral selection");
+    if ((ah != 0 && ah != al + 1) || al > 13) return hand_back(err, "successive approximation");
+    if (ns > 1 && mcu_blocks > 10) return hand_back(err, "MCU larger than 10 blocks");
+    for (int i = 0; i < ns; ++i) {
+      int8_t* s = sent[ci[i]];
+      if (ss > 0 && s[0] < 0) return hand_back(err, "AC scan before the component's DC");
+      for (int k = ss; k <= se; ++k) {
+        // first scan of a coefficient sent before, refinement of one never sent, or Ah that is not the last Al
+        if (ah == 0 ? s[k] >= 0 : s[k] != ah) return hand_back(err, "inconsistent progression");
+        s[k] = (int8_t)al;
+      }
+    }
+    const HuffTable* tab[kJpegMaxComp] = {};
+    ++cache->gen;
+    if (ss > 0 || ah == 0) {  // a DC refinement scan carries raw bits only
+      for (int i = 0; i < ns; ++i) {
+        const int th = ss > 0 ? ta[i] : td[i];
+        if (th > 3 || !(ss > 0 ? ac : dc)[th].present) {
+          err = "Failed to decode image: missing Huffman table";
+          return JpegStatus::Corrupt;
+        }
+        tab[i] = cache->get((ss > 0 ? ac : dc)[th], ss > 0);
+        if (!tab[i]) {
+          err = "Failed to decode image: bad Huffman table";
+          return JpegStatus::Corrupt;
+        }
+      }
+    }
+    pos += len;
+    // ---- entropy-coded segment ----
+    // A scan of one component is not interleaved: it covers the component's real blocks, row by row, and its
+    // restart interval counts them; the MCU padding of the grid (bw x bh) belongs to interleaved scans only.
+    const bool single = ns == 1;
+    const JpegCompDesc& d0 = info.comp[ci[0]];
+    const int sbw = single ? (d0.cw + 7) / 8 : info.mcux, sbh = single ? (d0.ch + 7) / 8 : info.mcuy;
+    const int64_t n_mcu = (int64_t)sbw * sbh;
+    const int kind = ss == 0 ? (ah == 0 ? 0 : 1) : (ah == 0 ? 2 : 3);
+    BitReader br{data + pos, data + n};
+    int pred[kJpegMaxComp] = {0, 0, 0};
+    int eobrun = 0;
+    int todo = ri;
+    auto block = [&](int i, int16_t* blk) -> bool {
+      switch (kind) {
+        case 0: return prog_dc_first(br, *tab[i], pred[i], al, blk);
+        case 1: prog_dc_refine(br, al, blk); return true;
+        case 2: return prog_ac_first(br, *tab[i], ss, se, al, eobrun, blk);
+        default: return prog_ac_refine(br, *tab[i], ss, se, al, eobrun, blk);
+      }
+    };
+    int next_rst = 0;
+    for (int64_t m = 0; m < n_mcu; ++m) {
+      if (ri) {
+        if (todo == 0) {
+          // the interval used up its bytes and RSTn, the expected n, follows at once; anything else makes libjpeg
+          // warn and resynchronise by guesswork
+          if (br.overran() || br.end - br.p < 2) {  // the file ends here
+            err = kTruncated;
+            return JpegStatus::Corrupt;
+          }
+          if (prog_leftover(br) || br.p[0] != 0xFF || br.p[1] != 0xD0 + next_rst)
+            return hand_back(err, "restart marker out of place");
+          next_rst = (next_rst + 1) & 7;
+          br.restart();
+          pred[0] = pred[1] = pred[2] = 0;
+          eobrun = 0;
+          todo = ri;
+        }
+        --todo;
+      }
+      const int my = (int)(m / sbw), mx = (int)(m % sbw);
+      if (single) {
+        if (!block(0, coef + d0.coef_off + ((int64_t)my * d0.bw + mx) * 64)) return hand_back(err, "coefficient value");
+      } else {
+        for (int i = 0; i < ns; ++i) {
+          const JpegCompDesc& d = info.comp[ci[i]];
+          for (int v = 0; v < d.v; ++v) {
+            int16_t* row = coef + d.coef_off + (((int64_t)my * d.v + v) * d.bw + (int64_t)mx * d.h) * 64;
+            for (int h = 0; h < d.h; ++h)
+              if (!block(i, row + h * 64)) return hand_back(err, "coefficient value");
+          }
+        }
+      }
+      // a marker cut the segment short and zero bits were read past it: libjpeg warns, and skips what follows
+      if (br.starved()) return hand_back(err, "scan data ends early");
+    }
+    if (br.truncated || br.overran()) {
+      err = kTruncated;
+      return JpegStatus::Corrupt;
+    }
+    if (prog_leftover(br)) return hand_back(err, "scan data left over");
+    // ---- markers up to the next scan or EOI ----
+    size_t q = (size_t)(br.p - data);
+    bool eoi = false;
+    for (;;) {
+      if (q < n && data[q] != 0xFF) return hand_back(err, "bytes between a scan and the next marker");
+      while (q < n && data[q] == 0xFF) ++q;
+      if (q >= n) {  // no EOI: libjpeg waits for more data, PIL raises
+        err = kTruncated;
+        return JpegStatus::Corrupt;
+      }
+      const int m = data[q++];
+      if (m == 0x00 || m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;
+      if (m == 0xD9) {
+        eoi = true;
+        break;
+      }
+      if (m == 0xD8) return hand_back(err, "SOI between scans");
+      if (q + 2 > n) {
+        err = "Failed to decode image: truncated marker";
+        return JpegStatus::Corrupt;
+      }
+      const size_t ml = be16(data + q);
+      if (ml < 2 || q + ml > n) {
+        err = "Failed to decode image: truncated marker segment";
+        return JpegStatus::Corrupt;
+      }
+      if (m == 0xDA) break;
+      if (m == 0xC4) {
+        if (!read_dht(data + q + 2, ml - 2, dc, ac)) {
+          err = "Failed to decode image: bad DHT";
+          return JpegStatus::Corrupt;
+        }
+      } else if (m == 0xDD) {
+        if (ml < 4) {
+          err = "Failed to decode image: bad DRI";
+          return JpegStatus::Corrupt;
+        }
+        ri = be16(data + q + 2);
+      } else if (!((m >= 0xE0 && m <= 0xEF) || m == 0xFE)) {
+        return hand_back(err, m == 0xDB ? "DQT between scans" : "marker between scans");
+      }
+      q += ml;
+    }
+    if (eoi) break;
+    pos = q;
+  }
+  // libjpeg smooths (and PIL returns the smoothed image) when the file ends before every coefficient is exact
+  for (int c = 0; c < info.ncomp; ++c)
+    for (int k = 0; k < 64; ++k)
+      if (sent[c][k] != 0) return hand_back(err, "incomplete progression");
+  return JpegStatus::Ok;
+}
 }  // namespace
 
 JpegStatus jpeg_decode_coefs(const uint8_t* data, size_t n, const JpegInfo& info, int16_t* coef, std::string& err) {
+  if (info.progressive) return decode_progressive(data, n, info, coef, err);
   thread_local std::unique_ptr<TableCache> cache;
   if (!cache) cache.reset(new TableCache());
   const HuffTable* dcp[kJpegMaxComp] = {};
@@ -702,7 +1057,51 @@ bool jpeg_compact_enabled() {
 
 int64_t jpeg_payload_bytes(const JpegInfo& info) { return info.compact_bytes >= 0 ? info.compact_bytes : info.coef_count * 2; }
 
+namespace {
+// Dense blocks into the compact payload, with the scan decoder's convention: the DC is always coded (bit 0 set,
+// its value stored even when 0), every other coefficient when it is not zero.
+void dense_to_compact(JpegInfo& info, const int16_t* coef, uint8_t* out) {
+  const int64_t tb = jpeg_total_blocks(info);
+  uint64_t* masks = (uint64_t*)out;
+  uint32_t* voff = (uint32_t*)(out + tb * 8);
+  const int64_t val_at = (tb * 12 + 15) & ~(int64_t)15;
+  int16_t* vals = (int16_t*)(out + val_at);
+  int64_t nv = 0;
+  uint8_t zigzag_of[64];  // natural index -> zigzag index
+  for (int k = 0; k < 64; ++k) zigzag_of[kNatural[k]] = (uint8_t)k;
+  for (int64_t b = 0; b < tb; ++b) {
+    const int16_t* blk = coef + b * 64;
+    voff[b] = (uint32_t)nv;
+    // most coefficients are zero: find the others four at a time, then visit only them, in zigzag order
+    uint64_t m = 1;
+    for (int w = 0; w < 16; ++w) {
+      uint64_t four;
+      std::memcpy(&four, blk + 4 * w, sizeof four);
+      if (four == 0) continue;
+      for (int j = 4 * w; j < 4 * w + 4; ++j) m |= (uint64_t)(blk[j] != 0) << zigzag_of[j];
+    }
+    masks[b] = m;
+    do {
+      vals[nv++] = blk[kNatural[__builtin_ctzll(m)]];
+      m &= m - 1;
+    } while (m);
+  }
+  info.compact_bytes = val_at + nv * 2;
+  info.cmask_off = 0;
+  info.cvoff_off = tb * 8;
+  info.cval_off = val_at;
+}
+}  // namespace
+
 JpegStatus jpeg_decode_compact(const uint8_t* data, size_t n, JpegInfo& info, uint8_t* out, std::string& err) {
+  if (info.progressive) {  // the scans refine dense blocks; the payload is packed after the last one
+    thread_local std::vector<int16_t> dense;
+    dense.resize((size_t)info.coef_count);
+    const JpegStatus st = decode_progressive(data, n, info, dense.data(), err);
+    if (st == JpegStatus::Ok) dense_to_compact(info, dense.data(), out);
+    if (dense.capacity() > ((size_t)16 << 20)) std::vector<int16_t>().swap(dense);  // do not pin a huge frame's
+    return st;
+  }
   thread_local std::unique_ptr<TableCache> cache;
   if (!cache) cache.reset(new TableCache());
   const HuffTable* dcp[kJpegMaxComp] = {};

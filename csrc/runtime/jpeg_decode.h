@@ -9,9 +9,14 @@
 // serial Huffman stream stays on a host thread, the per-pixel math moves to the GPU.
 //
 // Scope: baseline / extended-sequential Huffman (SOF0, SOF1), 8-bit samples, one interleaved scan with all
-// components, 1 (grayscale) or 3 (YCbCr) components in 4:4:4, 4:2:2 or 4:2:0, restart intervals.  Everything
-// else — progressive, arithmetic-coded, 12-bit, CMYK, RGB-coded, multi-scan, other samplings — is reported as
-// Unsupported and the caller sends the upload to the PIL fallback (server/decode_pool.py).  The same
+// components, 1 (grayscale) or 3 (YCbCr) components in 4:4:4, 4:2:2 or 4:2:0, restart intervals; and, when the
+// progressive switch is on (ARENA_JPEG_PROGRESSIVE, default 0, or the `progressive` argument of jpeg_parse),
+// progressive Huffman files (SOF2, T.81 Annex G) of the same frame geometry whose scans send every coefficient of
+// every component down to bit 0.  Everything else — arithmetic-coded, 12-bit, CMYK, RGB-coded, multi-scan
+// sequential, other samplings, progressive files with the switch off, with an incomplete or inconsistent
+// progression, more than kJpegMaxScans scans or a DQT between scans — is reported as Unsupported and the caller
+// sends the upload to the PIL fallback (server/decode_pool.py).  For a progressive file Unsupported can also come
+// from the decode functions, after jpeg_parse said Ok: callers route it to the same fallback.  The same
 // reconstruction arithmetic is available on the host (jpeg_coefs_to_rgb) as the bit-exact reference of the
 // kernels and as a host-only decode.
 #pragma once
@@ -46,6 +51,10 @@ struct JpegInfo {
   int64_t coef_count = 0;                // int16 coefficients of all components
   int64_t plane_bytes = 0;               // reconstructed sample planes of all components
   size_t scan_begin = 0;                 // first byte of the entropy-coded segment
+  // SOF2: the decode functions walk the scans themselves from `first_sos` (the length field of the first SOS
+  // segment; DHT, DRI and further SOS follow between scans).  restart_interval and dc / ac are the state there.
+  bool progressive = false;
+  size_t first_sos = 0;
   // compact payload (jpeg_decode_compact): its bytes and the byte offsets of its three arrays; -1 = dense int16
   int64_t compact_bytes = -1;
   int64_t cmask_off = 0, cvoff_off = 0, cval_off = 0;
@@ -54,20 +63,44 @@ struct JpegInfo {
 
 enum class JpegStatus : int { Ok = 0, Unsupported = 1, Corrupt = 2 };
 
-// Parse the markers up to the (single) scan.  `max_pixels` > 0 rejects larger frames as Corrupt with an
-// "image too large" message (the decode-bomb guard of processing/transforms.py).
+// A progressive file with more scans is handed back (each scan is a pass over the image: the decode-bomb guard;
+// PIL writes 10 scans for colour and 6 for grey, optimiser scripts stay below 16).
+constexpr int kJpegMaxScans = 32;
+
+// ARENA_JPEG_PROGRESSIVE (default 0), read once: the process default of jpeg_parse's `progressive`.  The setter
+// replaces it (for a process that decides after start-up) and returns the previous value.
+bool jpeg_progressive_enabled();
+bool jpeg_set_progressive_enabled(bool on);
+
+// Parse the markers up to the first scan.  `max_pixels` > 0 rejects larger frames as Corrupt with an
+// "image too large" message (the decode-bomb guard of processing/transforms.py).  `progressive`: 1 accepts SOF2
+// under the frame checks of SOF0/1, 0 reports it as Unsupported, -1 follows jpeg_progressive_enabled().
 //
 // Orientation, as cv2.imdecode honours it (processing/exif.py is the same rule in Python, for the PIL paths): the
 // first APP1 segment before SOS whose payload starts with "Exif\0\0" decides.  Its TIFF header ("II" or "MM", 42,
 // IFD0 offset) leads to IFD0; the first entry with tag 0x0112 counts when it is one SHORT with a value of 1..8.
 // Everything else is orientation 1: no such segment, another type or count, a value of 0 or 9, an IFD or entry
 // table that leaves the segment, an orientation that only XMP states.  Broken EXIF never changes the status.
-JpegStatus jpeg_parse(const uint8_t* data, size_t n, JpegInfo& info, std::string& err, int64_t max_pixels = 0);
+JpegStatus jpeg_parse(const uint8_t* data, size_t n, JpegInfo& info, std::string& err, int64_t max_pixels = 0,
+                      int progressive = -1);
 
 // Entropy-decode the scan: info.coef_count int16 quantized coefficients, natural order, one block after the
 // other (component c's block (by, bx) at comp[c].coef_off + (by * bw + bx) * 64).  A scan cut short by a
 // marker is padded with zero bits (libjpeg's warning, which PIL ignores); a file that simply ends inside the
 // scan is Corrupt ("image file is truncated", as PIL raises), like structurally broken streams.
+//
+// A progressive file (info.progressive) is decoded scan by scan into the same dense layout: DC scans interleaved
+// or not, single-component AC scans, first and refinement passes, EOB runs, restart intervals, and tables or a
+// restart interval redefined between scans.  A single-component scan of a 3-component frame covers the
+// component's real ceil(cw / 8) x ceil(ch / 8) blocks; the MCU padding of the grid keeps zero AC and the DC of the
+// interleaved DC scans.  The result is Ok only when it is what libjpeg computes without a warning; Unsupported
+// (hand the upload to PIL) when a scan header breaks G.1.1.1.1, the progression of some coefficient is
+// inconsistent (refinement before the first scan, a first scan twice, Ah not the previous Al, AC before DC) or at
+// EOI incomplete (libjpeg would smooth), there are more than kJpegMaxScans scans, a DQT or anything but DHT, DRI,
+// APPn and COM lies between scans, a value leaves int16, or the entropy-coded data is damaged where libjpeg warns:
+// a code that matches nothing, a refinement symbol of another magnitude than 1, a segment that a marker cuts short
+// or that leaves bytes over, a restart marker that is missing or not the expected RSTn.  (Baseline scans keep
+// their zero-bit padding of a segment cut short.)
 JpegStatus jpeg_decode_coefs(const uint8_t* data, size_t n, const JpegInfo& info, int16_t* coef, std::string& err);
 
 // The same scan into the compact payload the split decoder ships (3-4x fewer bytes than the dense blocks at q90:
@@ -75,7 +108,8 @@ JpegStatus jpeg_decode_coefs(const uint8_t* data, size_t n, const JpegInfo& info
 // row, then 1, 2): a uint64 mask (bit k: the coefficient at zigzag index k is coded), then per block the uint32
 // index of its first value, then the int16 values of every block in zigzag order (16-byte aligned array).  `out`
 // holds jpeg_compact_capacity(info) bytes; on success info.compact_bytes / cmask_off / cvoff_off / cval_off
-// describe what was written.  Status and error messages as jpeg_decode_coefs.
+// describe what was written.  Status and error messages as jpeg_decode_coefs.  A progressive file is decoded into
+// dense blocks in a thread-local scratch (released after use when above 16 MB) and packed after its last scan.
 JpegStatus jpeg_decode_compact(const uint8_t* data, size_t n, JpegInfo& info, uint8_t* out, std::string& err);
 int64_t jpeg_total_blocks(const JpegInfo& info);
 int64_t jpeg_compact_capacity(const JpegInfo& info);

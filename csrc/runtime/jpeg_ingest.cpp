@@ -96,7 +96,7 @@ void JpegIngest::run(Task& t) {
   auto up = std::make_shared<Upload>();
   std::string err;
   JpegStatus st = t.upload.empty() ? JpegStatus::Corrupt : jpeg_parse(data, t.upload.size(), up->info, err,
-                                                                      cfg_.max_image_pixels);
+                                                                      cfg_.max_image_pixels, cfg_.progressive);
   if (t.upload.empty()) err = "Failed to decode image: empty payload";
   if (st == JpegStatus::Unsupported) {
     {
@@ -146,10 +146,21 @@ void JpegIngest::run(Task& t) {
       }
     }
   }
+  if (st == JpegStatus::Unsupported) {  // a progressive file only its scans show to be outside the split decoder
+    up.reset();                         // its buffer back to the pool
+    {
+      std::lock_guard<std::mutex> lk(stats_mu_);
+      ++stats_.fallback;
+      stats_.cpu_decode_ms += thread_cpu_ms() - c0;
+    }
+    t.fallback(std::move(t.upload));
+    return;
+  }
   {
     std::lock_guard<std::mutex> lk(stats_mu_);
     if (st == JpegStatus::Ok) ++stats_.native;
     else ++stats_.errors;
+    if (st == JpegStatus::Ok && ji.progressive) ++stats_.progressive_decoded;
     stats_.cpu_decode_ms += thread_cpu_ms() - c0;
   }
   if (st != JpegStatus::Ok) return fail(t.done, err);

@@ -5,8 +5,10 @@
 // split JPEG decoder (runtime/jpeg_decode.h: marker parse + Huffman decode into a pinned HostBufferPool buffer)
 // and enqueue the result into the DynamicBatcher without a copy (enqueue_input); the instance reconstructs the
 // frame on the GPU.  `done` receives the batch result (or an error: a corrupt upload, a full queue).  Uploads the
-// split decoder does not cover (progressive JPEG, PNG, ...) are handed back through `fallback` untouched — the
-// caller decodes them its own way (PIL) and enqueues the pixels.  The reference decodes on the request thread
+// split decoder does not cover (PNG, CMYK, progressive JPEG unless IngestConfig::progressive or
+// ARENA_JPEG_PROGRESSIVE turns it on, and then still those whose progression is incomplete or inconsistent, which
+// only the entropy decode finds out) are handed back through `fallback` untouched — the caller decodes them its
+// own way (PIL) and enqueues the pixels.  The reference decodes on the request thread
 // (architectures/triton/gateway/app/pipeline.py:131-139 via cv2; here the ensemble's server process).
 #pragma once
 #include <atomic>
@@ -28,6 +30,7 @@ struct IngestConfig {
   int threads = 4;
   bool jpeg_device = true;  // false: reconstruct on the host threads (instances without the device half)
   int64_t max_image_pixels = 50000000;
+  int progressive = -1;  // SOF2 uploads: 1 split-decoded, 0 handed back, -1 the process default (jpeg_parse)
   int64_t buffer_cap = 1LL << 30;
   HostBufferPool::AllocFn host_alloc;
   HostBufferPool::FreeFn host_free;
@@ -35,6 +38,7 @@ struct IngestConfig {
 
 struct IngestStats {
   int64_t native = 0, fallback = 0, errors = 0;
+  int64_t progressive_decoded = 0;  // of native: progressive (SOF2) uploads
   double cpu_decode_ms = 0;
 };
 

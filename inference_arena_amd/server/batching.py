@@ -87,17 +87,24 @@ class AsyncBatcher:
         _enqueue_or_raise(self._b.enqueue(self._prep(x), done, int(export_to)))
         return self._check(await fut)
 
-    async def run_jpeg(self, data: bytes, decode, threads: int = 4, export_to: int = 0) -> dict:
+    async def run_jpeg(self, data: bytes, decode, threads: int = 4, export_to: int = 0,
+                       progressive: bool | None = None) -> dict:
         """An encoded upload through the native split decoder (csrc/runtime/jpeg_ingest.h: Huffman decode on C++
         threads into pinned memory, frame reconstructed on the GPU inside the batch); formats it does not cover
         go through ``await decode(data)`` (the caller's PIL path) and ``run``.  Decode failures raise
-        ValueError / TooLarge like the PIL path."""
+        ValueError / TooLarge like the PIL path.  ``progressive`` (read when the first call builds the ingest;
+        None = Settings.ARENA_JPEG_PROGRESSIVE): progressive JPEGs take the split decoder too, except those whose
+        scans leave some coefficient unfinished, which still go through ``decode``."""
         if getattr(self, "_ingest", None) is None:
             from ..ops import native
             from ..processing.transforms import max_image_pixels
+            from ..utils.settings import get_settings
 
+            if progressive is None:
+                progressive = bool(get_settings().ARENA_JPEG_PROGRESSIVE)
             self._ingest = native().JpegIngest(self._b, {"threads": int(threads),
-                                                         "max_image_pixels": int(max_image_pixels())})
+                                                         "max_image_pixels": int(max_image_pixels()),
+                                                         "progressive": bool(progressive)})
         loop = asyncio.get_running_loop()
         fut: asyncio.Future = loop.create_future()
 

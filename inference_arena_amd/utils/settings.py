@@ -71,6 +71,9 @@ class Settings(BaseModel):
     # likewise: 1 a gated level's first head conv runs as a class window and a box window over the tiles a kept box
     # tile reads (buckets >= 16), 0 whole and dense, 2 in every bucket
     ARENA_HEAD_SPLIT: int = 1
+    # 1 progressive (SOF2) JPEG uploads take the split decoder too (csrc/runtime/jpeg_decode.h), 0 they go to PIL.
+    # Also read natively as the process default (Executor.run on encoded bytes, configs without "progressive").
+    ARENA_JPEG_PROGRESSIVE: int = 0
 
     @classmethod
     def from_env(cls, env_file: str | Path = ".env", **overrides) -> "Settings":
