@@ -394,7 +394,7 @@ void xg_launch(const ConvParams& p, hipStream_t s) {
 }
 
 // split-K: tile variant (XG_VARIANTS id) x splits; a workspace of splits x B x Ho x Wo x Cout_pad fp32 (ConvParams
-// sk_ws, per executor slot and lane) holds the partial tiles
+// sk_ws, per executor slot) holds the partial tiles
 template <int WM, int WN, int TM, int TN>
 bool xg_launch_sk(const ConvParams& p, hipStream_t s, int splits) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;

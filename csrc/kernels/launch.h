@@ -73,7 +73,7 @@ struct ConvParams {
   // (engine/planner.py pack_conv_weight_x3), read by the x3g kernels (gemm_x3.hip); nullptr when absent
   const void* w3;
   // split-K x3g (kF32X3GSK): fp32 workspace for the partial tiles, splits x B x Ho x Wo x Cout_pad (executor: one
-  // per slot and lane); sk_splits is set by the launcher
+  // per slot); sk_splits is set by the launcher
   float* sk_ws;
   int64_t sk_ws_bytes;
   int sk_splits;

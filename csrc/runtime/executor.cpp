@@ -169,13 +169,8 @@ Executor::~Executor() {
     if (sl.copied) hipEventDestroy(sl.copied);
     if (sl.started) hipEventDestroy(sl.started);
     if (sl.done) hipEventDestroy(sl.done);
-    if (sl.fork_ev) hipEventDestroy(sl.fork_ev);
     for (hipEvent_t& e : sl.phase)
       if (e) hipEventDestroy(e);
-    for (int l = 0; l < kMaxLanes; ++l) {
-      if (sl.lane_ev[l]) hipEventDestroy(sl.lane_ev[l]);
-      if (sl.lane_stream[l]) hipStreamDestroy(sl.lane_stream[l]);
-    }
   }
   if (d_weights_) hipFree(d_weights_);
   if (compute_) hipStreamDestroy(compute_);
@@ -223,8 +218,8 @@ void Executor::alloc_slots() {
     // run up to 3 bytes past the last image of a full staging pool
     ARENA_HIP_CHECK(hipMalloc(&sl.d_in, in_bytes_total() + 256));
     ARENA_HIP_CHECK(hipMalloc(&sl.d_out, out_bytes_total()));
-    // split-K conv workspace (kF32X3GSK), one region per program lane: lanes run concurrently within a slot
-    ARENA_HIP_CHECK(hipMalloc(&sl.sk_ws, (size_t)sk_lane_bytes() * (kMaxLanes + 1)));
+    // split-K conv workspace (kF32X3GSK): the slot's batch runs on one stream, so its convs use it in turn
+    ARENA_HIP_CHECK(hipMalloc(&sl.sk_ws, (size_t)sk_ws_bytes()));
     // pinned host staging: the meta block plus the host-packed inputs of one full batch at the nominal frame size.
     // Split-decoded JPEGs need only their coefficients staged here (about 2/3 of an RGB frame at 4:2:0), so
     // pool_factor's extra device room needs no host twin; a batch that needs more grows it on demand
@@ -246,20 +241,6 @@ void Executor::alloc_slots() {
     }();
     ARENA_HIP_CHECK(hipEventCreateWithFlags(&sl.done, blocking ? hipEventBlockingSync : hipEventDefault));
   }
-}
-
-// Side streams of a slot, created when a lane bucket is captured on it (launch_graph runs lane segments there):
-// programs without lanes never create them (no extra queues per process).
-void Executor::ensure_lanes(Slot& sl) {
-  if (sl.fork_ev != nullptr) return;
-  bool lanes = false;
-  for (const OpRecord& r : prog_) lanes |= r[kLaneField] > 0;
-  if (!lanes) return;
-  for (int l = 0; l < kMaxLanes; ++l) {
-    ARENA_HIP_CHECK(hipStreamCreateWithFlags(&sl.lane_stream[l], hipStreamNonBlocking));
-    ARENA_HIP_CHECK(hipEventCreateWithFlags(&sl.lane_ev[l], hipEventDisableTiming));
-  }
-  ARENA_HIP_CHECK(hipEventCreateWithFlags(&sl.fork_ev, hipEventDisableTiming));
 }
 
 void Executor::set_weights(const void* host, size_t bytes) {
@@ -506,26 +487,9 @@ void Executor::autotune(Bucket& bk) {
   ARENA_HIP_CHECK(hipMemset(bk.d_arena[0], 0, std::max<int64_t>(bk.info.arena_bytes, 256)));
 }
 
-// Lanes pay off where one batch leaves most CUs idle (small buckets); for full batches the slots already overlap
-// batches on the compute streams and side streams only add contention (profiles/r4lanes/).
-static int lanes_max_batch() {
-  static const int v = [] {
-    const char* e = std::getenv("ARENA_LANES_MAX_BATCH");
-    return e != nullptr ? std::atoi(e) : 2;
-  }();
-  return v;
-}
-
-bool Executor::lanes_for(const Bucket& bk) const {
-  if (bk.info.B > lanes_max_batch()) return false;
-  for (const OpRecord& r : prog_)
-    if (r[kLaneField] >= 1 && r[kLaneField] <= kMaxLanes) return true;
-  return false;
-}
-
-// bytes of one lane's split-K workspace (ARENA_SPLITK_WS_MB, default 16): the largest bucket-1 split (the 7x7x960
+// bytes of a slot's split-K workspace (ARENA_SPLITK_WS_MB, default 16): the largest bucket-1 split (the 7x7x960
 // -> 320 classifier conv over 16 crops, 8 splits) needs 8 MB
-int64_t Executor::sk_lane_bytes() {
+int64_t Executor::sk_ws_bytes() {
   static const int64_t v = [] {
     const char* e = std::getenv("ARENA_SPLITK_WS_MB");
     return (int64_t)std::max(1, e != nullptr ? std::atoi(e) : 16) << 20;
@@ -534,14 +498,9 @@ int64_t Executor::sk_lane_bytes() {
 }
 
 void Executor::destroy_graphs(Bucket& bk, int s) {
-  if (bk.graph[s]) hipGraphExecDestroy(bk.graph[s]);
-  bk.graph[s] = nullptr;
   for (hipGraphExec_t g : bk.parts[s])
     if (g) hipGraphExecDestroy(g);
   bk.parts[s].clear();
-  for (auto& sg : bk.segs[s])
-    if (sg.g) hipGraphExecDestroy(sg.g);
-  bk.segs[s].clear();
 }
 
 void Executor::capture(Bucket& bk, int s) {
@@ -584,93 +543,35 @@ void Executor::capture(Bucket& bk, int s) {
     ARENA_HIP_CHECK(hipGraphDestroy(g));
     return ge;
   };
-  if (!lanes_for(bk)) {
-    // buckets of >= 16 are captured in parts (launch_graph decides per batch whether to wait between them)
-    std::vector<size_t> cuts{0};
-    if (bk.info.B >= 16)
-      for (double f : stagger_) {
-        const size_t k = (size_t)std::lround(f * (double)prog_.size());
-        if (k > cuts.back() && k < prog_.size()) cuts.push_back(k);
-      }
-    if (cuts.size() > 1) {
-      cuts.push_back(prog_.size());
-      for (size_t i = 0; i + 1 < cuts.size(); ++i) bk.parts[s].push_back(capture_range(cuts[i], cuts[i + 1]));
-    } else {
-      bk.graph[s] = capture_range(0, prog_.size());
+  // buckets of >= 16 are captured in parts (launch_graph decides per batch whether to wait between them)
+  std::vector<size_t> cuts{0};
+  if (bk.info.B >= 16)
+    for (double f : stagger_) {
+      const size_t k = (size_t)std::lround(f * (double)prog_.size());
+      if (k > cuts.back() && k < prog_.size()) cuts.push_back(k);
     }
-    return;
-  }
-  // Lanes: every maximal run of ops with one lane value becomes a linear graph of its own; launch_graph() forks
-  // the side streams (ensure_lanes) off the slot's stream at a lane run and joins them at the next lane-0 run.
-  ensure_lanes(sl);
-  auto lane_of = [&](size_t i) {
-    const int64_t l = prog_[i][kLaneField];
-    return l >= 1 && l <= kMaxLanes ? (int)l : 0;
-  };
-  for (size_t a = 0; a < prog_.size();) {
-    size_t b = a + 1;
-    while (b < prog_.size() && lane_of(b) == lane_of(a)) ++b;
-    Bucket::Seg sg;
-    sg.lane = lane_of(a);
-    sg.g = capture_range(a, b);
-    bk.segs[s].push_back(sg);
-    a = b;
-  }
+  cuts.push_back(prog_.size());
+  for (size_t i = 0; i + 1 < cuts.size(); ++i) bk.parts[s].push_back(capture_range(cuts[i], cuts[i + 1]));
 }
 
 void Executor::launch_graph(Bucket& bk, int s, hipStream_t st, int n_live) {
-  if (bk.segs[s].empty()) {
-    if (!bk.parts[s].empty()) {
-      // and only while the device is saturated: two other batches still in flight
-      int others = 0;
-      for (int k = 0; k < n_slots_; ++k) others += k != s && slots_[k].busy ? 1 : 0;
-      const bool gate = n_live < 0 || (n_live >= std::min(stagger_min_batch_, bk.info.B) && others >= 2);
-      // part i (all but the last) after the previously launched batch finished its part i: at most one batch in
-      // each gated part at a time, any number in the last (an event already passed, or re-recorded by a later
-      // launch of that slot, costs nothing)
-      const Slot* prev = gate && last_launched_ >= 0 && last_launched_ != s ? &slots_[last_launched_] : nullptr;
-      const size_t np = bk.parts[s].size();
-      for (size_t i = 0; i < np; ++i) {
-        if (prev && i + 1 < np) ARENA_HIP_CHECK(hipStreamWaitEvent(st, prev->phase[i], 0));
-        ARENA_HIP_CHECK(hipGraphLaunch(bk.parts[s][i], st));
-        ARENA_HIP_CHECK(hipEventRecord(slots_[s].phase[i], st));
-      }
-      last_launched_ = s;
-      return;
-    }
-    ARENA_HIP_CHECK(hipGraphLaunch(bk.graph[s], st));
-    return;
+  // A single part is a bare graph launch.  A bucket captured in several parts is staggered, for a full enough batch
+  // and only while the device is saturated: two other batches still in flight.
+  const size_t np = bk.parts[s].size();
+  const bool staggered = np > 1;
+  int others = 0;
+  for (int k = 0; k < n_slots_; ++k) others += k != s && slots_[k].busy ? 1 : 0;
+  const bool gate = staggered && (n_live < 0 || (n_live >= std::min(stagger_min_batch_, bk.info.B) && others >= 2));
+  // part i (all but the last) after the previously launched batch finished its part i: at most one batch in
+  // each gated part at a time, any number in the last (an event already passed, or re-recorded by a later
+  // launch of that slot, costs nothing)
+  const Slot* prev = gate && last_launched_ >= 0 && last_launched_ != s ? &slots_[last_launched_] : nullptr;
+  for (size_t i = 0; i < np; ++i) {
+    if (prev && i + 1 < np) ARENA_HIP_CHECK(hipStreamWaitEvent(st, prev->phase[i], 0));
+    ARENA_HIP_CHECK(hipGraphLaunch(bk.parts[s][i], st));
+    if (staggered) ARENA_HIP_CHECK(hipEventRecord(slots_[s].phase[i], st));
   }
-  Slot& sl = slots_[s];
-  bool forked[kMaxLanes] = {};
-  bool fork_recorded = false;
-  auto join = [&]() {
-    for (int l = 0; l < kMaxLanes; ++l)
-      if (forked[l]) {
-        ARENA_HIP_CHECK(hipEventRecord(sl.lane_ev[l], sl.lane_stream[l]));
-        ARENA_HIP_CHECK(hipStreamWaitEvent(st, sl.lane_ev[l], 0));
-        forked[l] = false;
-      }
-    fork_recorded = false;
-  };
-  for (const Bucket::Seg& sg : bk.segs[s]) {
-    if (sg.lane == 0) {
-      join();
-      ARENA_HIP_CHECK(hipGraphLaunch(sg.g, st));
-      continue;
-    }
-    const int l = sg.lane - 1;
-    if (!forked[l]) {
-      if (!fork_recorded) {  // everything before the lane region on the slot's stream
-        ARENA_HIP_CHECK(hipEventRecord(sl.fork_ev, st));
-        fork_recorded = true;
-      }
-      ARENA_HIP_CHECK(hipStreamWaitEvent(sl.lane_stream[l], sl.fork_ev, 0));
-      forked[l] = true;
-    }
-    ARENA_HIP_CHECK(hipGraphLaunch(sg.g, sl.lane_stream[l]));
-  }
-  join();
+  if (staggered) last_launched_ = s;
 }
 
 uint8_t* Executor::resolve(Bucket& bk, Slot& sl, int64_t buf, int64_t coff, int eb) {
@@ -696,8 +597,8 @@ uint8_t* Executor::resolve(Bucket& bk, Slot& sl, int64_t buf, int64_t coff, int 
 // Head gate (head_gate.h): a pair's class conv (op i + 1) is enqueued before its box conv (op i), which then skips
 // the tiles without a passing class logit.  Swapping the two cannot break the arena layout: they are adjacent and
 // independent, so the buffers of both are live across both positions in either order.  A pair stays in program
-// order and ungated when its two ops are not both in this enqueue segment (a stagger split point or a lane boundary
-// between them, a single op of the debug modes), when an op is being timed (force_impl: timings stay dense-cost, and
+// order and ungated when its two ops are not both in this enqueue segment (a stagger split point between them,
+// a single op of the debug modes), when an op is being timed (force_impl: timings stay dense-cost, and
 // the logits buffer holds nothing meaningful then) and when the kernel chosen for the box conv is not an x3hg
 // fused-1x1 variant.  The gate is advisory: an ungated op is merely slower, never wrong.
 std::vector<size_t> Executor::exec_plan(const std::vector<OpRecord>& prog, const Bucket& bk, int op_offset,
@@ -759,8 +660,8 @@ std::vector<Executor::Step> Executor::launch_plan(const std::vector<OpRecord>& p
   return steps;
 }
 
-void Executor::enqueue_program(const std::vector<OpRecord>& prog, Bucket& bk, Slot& sl, hipStream_t s_main,
-                               int op_offset, int force_impl) {
+void Executor::enqueue_program(const std::vector<OpRecord>& prog, Bucket& bk, Slot& sl, hipStream_t s, int op_offset,
+                               int force_impl) {
   Ctrl* ctrl = (Ctrl*)resolve(bk, sl, BUF_CTRL, 0, 1);
   const ImageMeta* meta = (const ImageMeta*)resolve(bk, sl, BUF_META, 0, 1);
   const uint8_t* pool = resolve(bk, sl, BUF_POOL, 0, 1);
@@ -769,8 +670,6 @@ void Executor::enqueue_program(const std::vector<OpRecord>& prog, Bucket& bk, Sl
   auto bdev = [&](int64_t kind) -> const int* { return kind == BATCH_CROPS ? &ctrl->n_crops : &ctrl->n_images; };
   const uint8_t* W = d_weights_;
 
-  // Lane ops (kLaneField) run in program order here: the lanes' side streams are driven by launch_graph() over
-  // per-lane captured segments, not by forking inside one capture.
   const std::vector<Step> steps = launch_plan(prog, bk, op_offset, force_impl);
   auto marks_of = [&](const HeadGatePair* gp) {
     return (int*)(bk.d_arena[sl.idx] + bk.marks_off[(size_t)(gp - gate_pairs_.data())]);
@@ -778,7 +677,6 @@ void Executor::enqueue_program(const std::vector<OpRecord>& prog, Bucket& bk, Sl
   for (const Step& step : steps) {
     const size_t oi = step.pos;
     const OpRecord& r = prog[oi];
-    hipStream_t s = s_main;
     if (step.kind == LAUNCH_MARK) {  // r = the pair's box conv: the level's class logits follow its 1x1 output
       HeadMarkParams m{};
       m.n_levels = 1;
@@ -830,12 +728,8 @@ void Executor::enqueue_program(const std::vector<OpRecord>& prog, Bucket& bk, Sl
         p.B = batch(r[30]);
         p.bdev = bdev(r[30]);
         if (r[41] != 0) p.w3 = W + r[40];  // fp32: pre-split bf16 weight planes for the x3g kernels
-        {
-          const int64_t ln = r[kLaneField];
-          const int li = ln >= 1 && ln <= kMaxLanes ? (int)ln : 0;
-          p.sk_ws = (float*)((uint8_t*)sl.sk_ws + (size_t)li * sk_lane_bytes());
-          p.sk_ws_bytes = sk_lane_bytes();
-        }
+        p.sk_ws = sl.sk_ws;
+        p.sk_ws_bytes = sk_ws_bytes();
         if (r[1] == BUF_POOL) {  // the stem conv samples the letterboxed images itself (fp32 x3-h16 kernel)
           if (!f32 || r[30] != 0) throw std::runtime_error("executor: letterbox-source conv must be fp32 over images");
           p.x = nullptr;

@@ -43,11 +43,6 @@ namespace arena {
 
 constexpr int kOpFields = 48;
 constexpr int kDtypeField = 47;  // per-op activation precision: 0 bf16, 1 exact fp32
-// Per-op stream lane (planner.OP_LANE_FIELD): 0 = the batch's stream; 1..kMaxLanes = a side stream forked from
-// it before the first op of a run of lane ops and joined back at the next lane-0 op (independent branches such
-// as the three Detect-head levels run concurrently, inside the captured graph as parallel branches).
-constexpr int kLaneField = 46;
-constexpr int kMaxLanes = 3;
 constexpr int kMaxSlots = 6;
 constexpr int kMaxStaggerParts = 5;  // staggered launch: at most 4 split points (executor.cpp launch_graph)
 constexpr int kMaxEstBuckets = 257;  // completion-time estimates per bucket size (larger buckets share the last)
@@ -222,7 +217,7 @@ class Executor : public BatchInstance {
     // device
     uint8_t* d_in = nullptr;   // ctrl | meta | pool
     uint8_t* d_out = nullptr;  // det_count | det | topk
-    float* sk_ws = nullptr;    // split-K conv workspace: (kMaxLanes + 1) x sk_lane_bytes()
+    float* sk_ws = nullptr;    // split-K conv workspace: sk_ws_bytes()
     // pinned host
     uint8_t* h_in = nullptr;
     size_t h_cap = 0;  // bytes of h_in (meta + host-packed inputs; grows on demand)
@@ -237,8 +232,6 @@ class Executor : public BatchInstance {
     // batch's work.  More slots than streams lets the next batches' packing
     // and H2D copies run ahead while the device is busy.
     hipStream_t stream = nullptr;  // stream of the slot's current batch
-    hipStream_t lane_stream[kMaxLanes] = {};  // side streams of program lanes (kLaneField)
-    hipEvent_t fork_ev = nullptr, lane_ev[kMaxLanes] = {};
     int idx = 0;
     std::chrono::steady_clock::time_point t_submit{};  // host time of the submit (adaptive completion wait)
     bool polled = false;  // a completion test found the batch running (its completion time is a real sample)
@@ -252,19 +245,9 @@ class Executor : public BatchInstance {
     BucketInfo info;
     uint8_t* d_arena[kMaxSlots] = {};  // per slot (all aliased when concurrency is off)
     int last_slot = 0;                 // slot whose arena read_arena() inspects
-    hipGraphExec_t graph[kMaxSlots] = {};
-    // staggered launch (ARENA_STAGGER): the program as consecutive parts split at the stagger points, one graph
-    // each (graph[s] unused then)
+    // the program as consecutive parts, one graph each: split at the stagger points (ARENA_STAGGER), a single part
+    // when the bucket has no stagger cut
     std::vector<hipGraphExec_t> parts[kMaxSlots];
-    // Lane buckets (program lanes, B <= lanes_max_batch()): the program as contiguous single-lane segments, one
-    // graph each; launch_graph() runs lane segments on the slot's side streams between fork / join events.
-    // (A single graph with forked branches made HIP's graph launch segfault with GPU_MAX_HW_QUEUES < 4 from the
-    // batcher's instance thread: profiles/r5lanes/README.md.)
-    struct Seg {
-      int lane = 0;
-      hipGraphExec_t g = nullptr;
-    };
-    std::vector<Seg> segs[kMaxSlots];
     std::vector<int16_t> impl;  // per op of prog_: conv kernel family chosen by autotune (0 = default)
     // the captured graphs' kernels in launch order, as indices into prog_ (program order except for the swapped
     // head-gate pairs), and the ops that run with a tile gate
@@ -282,18 +265,16 @@ class Executor : public BatchInstance {
   };
 
   void alloc_slots();
-  void ensure_lanes(Slot& sl);
   void sync_slots();
   void free_arenas(Bucket& bk);
   void capture(Bucket& bk, int slot);
   void wait_done(Slot& sl);
   void note_done(Slot& sl);
   void release_copy(Slot& sl);
-  static int64_t sk_lane_bytes();
+  static int64_t sk_ws_bytes();
   uint64_t copy_release_n_ = 0;
   void launch_graph(Bucket& bk, int slot, hipStream_t st, int n_live = -1);  // n_live: images of the batch
   void destroy_graphs(Bucket& bk, int slot);
-  bool lanes_for(const Bucket& bk) const;
   void enqueue_program(const std::vector<OpRecord>& prog, Bucket& bk, Slot& sl, hipStream_t s,
                        int op_offset = 0, int force_impl = 0);
   void autotune(Bucket& bk);
