@@ -16,6 +16,10 @@
 // pixels (M) with weights as the A operand (v_mfma_f32_16x16x32_bf16); the
 // 3x3 takes its B operand straight from the halo-padded U buffer.
 //
+// Rounding points: every stage accumulates in fp32 and applies bias + SiLU in fp32; T, U and the updated Tc are
+// stored to LDS as bf16 (pack4, round to nearest even; the shortcut is added to the fp32 value before that
+// store), y is one bf16 store.  tests/bf16_bounds.py (c3_refs / c3_emulate) models exactly these stores.
+//
 // LDS rows are C*2 + 16 bytes: the 16-byte pad staggers consecutive pixels
 // across banks, so the 16 lanes of a ds_read_b128 group hit distinct slots.
 #include <type_traits>

@@ -246,6 +246,43 @@ def c3_x3_nhwc(x: torch.Tensor, cv12, bottleneck, cv3) -> torch.Tensor:
     return y
 
 
+def c3_fused_nhwc(x: torch.Tensor, cv12, bottleneck, cv3, *, n: int = 1, shortcut: bool = True, x_coff: int = 0,
+                  c1: int | None = None, out: torch.Tensor | None = None, out_coff: int = 0,
+                  bdev: torch.Tensor | None = None) -> torch.Tensor:
+    """bf16 YOLOv5 C3 block as one kernel (csrc/kernels/c3_fused.hip): C1 32 / c_ 16 / n 1 / shortcut, C1 64 / c_ 32 /
+    n 2 / shortcut or C1 128 / c_ 32 / n 1 / no shortcut, on a map of whole 8 x 16 tiles.  ``cv12`` = (w [2c_, C1, 1,
+    1], b) of cv1|cv2 stacked, ``bottleneck`` = ((w1 [c_, c_, 1, 1], b1), (w2 [c_, c_, 3, 3], b2)) — one weight set,
+    applied ``n`` times —, ``cv3`` = (w [2c_, 2c_, 1, 1], b); BN folded.  Reads channels [x_coff, x_coff + C1) of
+    ``x``; ``out``: a contiguous bf16 [B, H, W, >= out_coff + 2c_] tensor to write channels [out_coff, out_coff +
+    2c_) of (the rest is left as it is) instead of a fresh one."""
+    B, H, W, Cx = x.shape
+    (w1, b1), (w2, b2) = bottleneck
+    ch = w1.shape[0]
+    c1 = c1 or cv12[0].shape[1]
+    if x.dtype != torch.bfloat16 or not x.is_contiguous() or x_coff < 0 or x_coff + c1 > Cx:
+        raise ValueError("c3_fused_nhwc: x must be contiguous bf16 [B, H, W, >= x_coff + C1]")
+    if x_coff % 8 or out_coff % 4:  # 16-byte loads, 8-byte stores
+        raise ValueError("c3_fused_nhwc: x_coff must be a multiple of 8 and out_coff of 4")
+    if cv12[0].shape[:2] != (2 * ch, c1) or cv3[0].shape[:2] != (2 * ch, 2 * ch) or w2.shape != (ch, ch, 3, 3):
+        raise ValueError("c3_fused_nhwc: weight shapes do not form a C3 block")
+    if out is None:
+        out = torch.empty(B, H, W, 2 * ch, dtype=torch.bfloat16, device=x.device)
+    if (out.shape[:3] != (B, H, W) or out_coff < 0 or out.shape[3] < out_coff + 2 * ch or out.dtype != torch.bfloat16
+            or out.device != x.device or not out.is_contiguous()):
+        raise ValueError(f"c3_fused_nhwc: out {tuple(out.shape)} {out.dtype} does not fit the block's output")
+    w1p = torch.zeros(ch, 32, 1, 1)  # [c_][32]: the kernel reads T's first 32 channels, columns past c_ are zero
+    w1p[:, :ch] = w1.detach().float().reshape(ch, ch, 1, 1)
+    dev = {}
+    for k, (w, b) in (("12", cv12), ("b1", (w1p, b1)), ("b2", (w2, b2)), ("3", cv3)):
+        wt, bt = pack_weights(w, b, x.device, "bf16")[:2]
+        dev["w" + k], dev["b" + k] = wt, bt
+    native().c3_block({"x": _ptr(x, x_coff), "xs": Cx, "B": B, "H": H, "W": W, "bdev": _ptr(bdev), "C1": c1, "CH": ch,
+                       "NB": n, "res": int(shortcut), **{k: _ptr(v) for k, v in dev.items()},
+                       "y": _ptr(out, out_coff), "ys": out.shape[3], "stream": _stream(), "f32": 0})
+    torch.cuda.synchronize(x.device)  # keep the packed weights alive until the kernel ran
+    return out
+
+
 def sppf_nhwc(buf: torch.Tensor, C: int) -> torch.Tensor:
     """In place: buf[..., C:4C] = cascaded 5x5 max pools of buf[..., :C]."""
     B, H, W, Ct = buf.shape
@@ -304,9 +341,10 @@ def avgpool_nhwc(x: torch.Tensor) -> torch.Tensor:
 
 
 def head_pool_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, act: str | None = "relu6",
-                   bdev: torch.Tensor | None = None) -> torch.Tensor:
+                   bdev: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
     """mean over pixels of act(conv1x1(x, w) + b): [B,H,W,C] -> [B, N] (head_pool.hip); bf16 in/out, or fp32
-    in/out (fp32-accurate triple-bf16-split kernel) for a float32 ``x``."""
+    in/out (fp32-accurate triple-bf16-split kernel) for a float32 ``x``.  ``out``: a contiguous [B, N] tensor of
+    ``x``'s dtype to write into (rows past the live count ``bdev`` keep their contents) instead of a fresh one."""
     from ..engine.planner import ACT, pack_conv_weight
 
     B, H, W, C = x.shape
@@ -315,7 +353,9 @@ def head_pool_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, act: str |
     wb, bb, kpad, npad = pack_conv_weight(w, b, "fp32" if f32 else "bf16")
     wd = torch.frombuffer(bytearray(wb), dtype=torch.float32 if f32 else torch.bfloat16).to(x.device)
     bd = torch.frombuffer(bytearray(bb), dtype=torch.float32).to(x.device)
-    y = torch.empty(B, N, dtype=x.dtype, device=x.device)
+    y = out if out is not None else torch.empty(B, N, dtype=x.dtype, device=x.device)
+    if y.shape != (B, N) or y.dtype != x.dtype or y.device != x.device or not y.is_contiguous():
+        raise ValueError(f"head_pool_nhwc: out {tuple(y.shape)} {y.dtype} does not fit the pooled output")
     native().head_pool({"x": _ptr(x), "xs": C, "HW": H * W, "K": C, "w": _ptr(wd), "Kpad": kpad, "bias": _ptr(bd),
                         "N": N, "Npad": npad, "y": _ptr(y), "ys": N, "act": ACT[act], "B": B, "bdev": _ptr(bdev),
                         "stream": _stream(), "f32": int(f32)})

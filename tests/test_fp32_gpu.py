@@ -327,6 +327,26 @@ def test_conv_x3_split_matches_fp64(device, B, H, Cin, Cout, k, s, act, res):
     assert ran >= 12
 
 
+@pytest.mark.parametrize("B,live", [(17, None), (32, 16), (32, 17)])
+def test_fc_f32_crop_tiles(device, B, live):
+    """The fp32 split-K FC (impl 106, fc_splitk.hip) over its 16-crop tiles: B 17 is two tiles, the second with one
+    live row; a device-side live count of 16 ends at a tile border, 17 one row past it.  Cout 1000: the last
+    32-class tile holds 8.  Rows past the live count keep their contents."""
+    g = torch.Generator().manual_seed(B * 5 + (live or 0))
+    x = torch.randn(B, 1280, 1, 1, generator=g)
+    w = torch.randn(1000, 1280, 1, 1, generator=g) / 1280 ** 0.5
+    b = torch.randn(1000, generator=g)
+    ref = F.conv2d(x.double(), w.double(), b.double())
+    scale = F.conv2d(x.double().abs(), w.double().abs(), b.double().abs())
+    out = torch.full((B, 1, 1, 1000), -7.0, device=device)
+    bdev = None if live is None else torch.tensor([live], dtype=torch.int32, device=device)
+    AF.conv2d_nhwc(_nhwc(x).to(device), w, b, act=None, impl=106, out=out, bdev=bdev)
+    torch.cuda.synchronize()
+    n = B if live is None else live
+    _fp32_check(out.permute(0, 3, 1, 2)[:n], ref[:n], scale[:n])
+    assert torch.all(out[n:] == -7.0), "rows past the live count must not be written"
+
+
 def test_conv_f32_channel_slices(device):
     """Reads channels [x_coff, x_coff + Cin) of a wider buffer and stores into a channel slice (concat)."""
     g = torch.Generator().manual_seed(7)
