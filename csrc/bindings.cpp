@@ -303,6 +303,44 @@ void py_tensor_in(const py::dict& d) {
   tensor_in_s2d(p, stream_of(d));
 }
 
+// fp32 detector front end on its own (csrc/kernels/stem_x3.hip): src 0 letterbox, 2 request tensors.
+void py_stem_s2_f32(const py::dict& d) {
+  prepare_kernels();
+  StemFusedParams p{};
+  p.src = req<int>(d, "src");
+  p.pool = ptr<const uint8_t*>(d, "pool");
+  p.meta = ptr<const ImageMeta*>(d, "meta");
+  p.ctrl = ptr<const Ctrl*>(d, "ctrl");
+  p.cap = req<int>(d, "cap");
+  p.S = req<int>(d, "S");
+  p.KS = 3;
+  p.w = ptr<const void*>(d, "w");
+  p.bias = ptr<const float*>(d, "bias");
+  p.Cout = 16;
+  p.act = 1;
+  p.w2 = ptr<const void*>(d, "w2");
+  p.bias2 = ptr<const float*>(d, "bias2");
+  p.Cout2 = 32;
+  p.act2 = get<int>(d, "act2", 1);
+  p.y2 = ptr<void*>(d, "y");
+  p.y2s = req<int>(d, "ys");
+  stem_s2_f32(p, stream_of(d));
+}
+
+// {"name", "input", "in_dims", "output", "out_dims", "max_batch_size", "platform", "versions"} -> the contract
+KServeTensorModel tensor_model_of(const py::dict& d) {
+  KServeTensorModel m;
+  m.name = req<std::string>(d, "name");
+  m.input = req<std::string>(d, "input");
+  m.output = req<std::string>(d, "output");
+  m.in_dims = req<std::vector<int64_t>>(d, "in_dims");
+  m.out_dims = req<std::vector<int64_t>>(d, "out_dims");
+  m.max_batch_size = get<int>(d, "max_batch_size", 0);
+  m.platform = get<std::string>(d, "platform", m.platform);
+  m.versions = get<std::vector<std::string>>(d, "versions", {});
+  return m;
+}
+
 void py_nms(const py::dict& d) {
   prepare_kernels();
   NmsParams p{};
@@ -713,6 +751,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("detect_decode", &py_decode);
   m.def("yolo_raw", &py_yolo_raw);
   m.def("tensor_in_s2d", &py_tensor_in);
+  m.def("stem_s2_f32", &py_stem_s2_f32);
   m.def("nms", &py_nms);
   m.def("crop_plan", &py_crop_plan);
   m.def("crop_gather_s2d", &py_crop_gather);
@@ -933,8 +972,9 @@ PYBIND11_MODULE(_C, m) {
       });
 
   py::class_<EchoInstance, std::shared_ptr<EchoInstance>>(m, "EchoInstance")
-      .def(py::init<int, int, int, int, int64_t>(), py::arg("slots") = 2, py::arg("max_batch") = 32,
-           py::arg("max_det") = 4, py::arg("latency_us") = 0, py::arg("staging_cap") = 0);
+      .def(py::init<int, int, int, int, int64_t, int64_t>(), py::arg("slots") = 2, py::arg("max_batch") = 32,
+           py::arg("max_det") = 4, py::arg("latency_us") = 0, py::arg("staging_cap") = 0,
+           py::arg("raw_out_bytes") = 0);
 
   py::class_<DynamicBatcher>(m, "DynamicBatcher")
       .def(py::init([](py::list executors, const py::dict& cfg) {
@@ -1252,6 +1292,15 @@ PYBIND11_MODULE(_C, m) {
                c.progressive = cfg["progressive"].cast<bool>() ? 1 : 0;
              c.decode_buffer_cap = get<int64_t>(cfg, "decode_buffer_cap", c.decode_buffer_cap);
              c.kserve_model = get<std::string>(cfg, "kserve_model", c.kserve_model);
+             c.body_pool_depth = get<int>(cfg, "body_pool_depth", c.body_pool_depth);
+             if (cfg.contains("tensor_models"))  // dicts as tensor_model_of + "batcher" (kept alive with cfg)
+               for (auto h : cfg["tensor_models"].cast<py::list>()) {
+                 const py::dict td = h.cast<py::dict>();
+                 TensorModelEntry e;
+                 e.model = tensor_model_of(td);
+                 e.batcher = &td["batcher"].cast<DynamicBatcher&>();
+                 c.tensor_models.push_back(std::move(e));
+               }
              // decoded uploads live in pinned memory when a GPU is present (the executor DMAs from them)
              int ndev = 0;
              const bool gpu = hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
@@ -1270,7 +1319,7 @@ PYBIND11_MODULE(_C, m) {
              py::gil_scoped_release nogil;
              return new HttpFrontEnd(&batcher, dc, std::move(labels), c);
            }),
-           py::keep_alive<1, 2>())
+           py::keep_alive<1, 2>(), py::keep_alive<1, 5>())
       // handler mode: HTTP/multipart natively, the request handler in Python (take / complete)
       .def(py::init([](const py::dict& cfg) {
         FrontConfig c;
@@ -1342,6 +1391,22 @@ PYBIND11_MODULE(_C, m) {
              d["progressive_decoded"] = s.progressive_decoded;
              d["bodies_recycled"] = s.bodies_recycled;
              d["bodies_allocated"] = s.bodies_allocated;
+             d["bodies_retained_bytes"] = s.bodies_retained_bytes;
+             d["bodies_budget_bytes"] = s.bodies_budget_bytes;
+             d["bodies_over_budget"] = s.bodies_over_budget;
+             py::dict tms;
+             for (const TensorModelStats& t : s.tensor_models) {
+               py::dict e;
+               e["requests"] = t.requests;
+               e["items"] = t.items;
+               e["ok"] = t.ok;
+               e["failed"] = t.failed;
+               e["request_us"] = t.request_us;
+               e["queue_us"] = t.queue_us;
+               e["compute_us"] = t.compute_us;
+               tms[py::str(t.name)] = e;
+             }
+             d["tensor_models"] = tms;
              d["cpu_parse_ms"] = s.cpu_parse_ms;
              d["cpu_decode_ms"] = s.cpu_decode_ms;
              d["cpu_json_ms"] = s.cpu_json_ms;
@@ -1357,6 +1422,32 @@ PYBIND11_MODULE(_C, m) {
         py::gil_scoped_release nogil;
         f.stop();
       });
+  // tensor-model wire layer (runtime/kserve.h) on its own, for tests: the parser raises ValueError with the
+  // message a client would get in the 400 body
+  m.def("kserve_parse_tensor_input", [](const std::string& body, int64_t ihcl, const py::dict& model) {
+    KServeTensorRequest r;
+    std::string err;
+    if (!kserve_parse_tensor_input(body, ihcl, tensor_model_of(model), r, err)) throw py::value_error(err);
+    py::dict d;
+    d["id"] = r.id;
+    d["off"] = r.off;
+    d["n"] = r.n;
+    d["item_bytes"] = r.item_bytes;
+    d["batch_dim"] = r.batch_dim;
+    return d;
+  });
+  m.def("kserve_build_tensor_response",
+        [](const py::dict& model, const std::string& id, bool batch_dim, const std::vector<std::string>& items) {
+          std::vector<std::vector<uint8_t>> raw;
+          for (const std::string& s : items) raw.emplace_back(s.begin(), s.end());
+          std::vector<const std::vector<uint8_t>*> ptrs;
+          for (const auto& v : raw) ptrs.push_back(&v);
+          int64_t ihcl = -1;
+          const std::string out = kserve_build_tensor_response(tensor_model_of(model), id, batch_dim, ptrs, &ihcl);
+          return py::make_tuple(py::bytes(out), ihcl);
+        });
+  m.def("kserve_tensor_model_metadata",
+        [](const py::dict& model) { return kserve_tensor_model_metadata(tensor_model_of(model)); });
   // native gateway: /predict forwarded to a model server's KServe endpoint (FrontConfig upstream_*)
   m.def(
       "http_proxy_front",

@@ -432,10 +432,11 @@ void crop_gather_s2d(const CropGatherParams& p, hipStream_t s);
 
 // ---------------------------------------------------------------- fused preprocessing + stem conv
 // src 0: letterbox (images) -> YOLOv5nu stem (3x3 over s2d, 16 -> 16, SiLU);
-// src 1: crop gather (crops) -> MobileNetV2 stem (2x2 over s2d, 16 -> 32, ReLU6).
+// src 1: crop gather (crops) -> MobileNetV2 stem (2x2 over s2d, 16 -> 32, ReLU6);
+// src 2: fp32 NCHW [3, S, S] request tensors in the pool -> YOLOv5nu stem (fp32 programs only, stem_s2_f32).
 // The s2d input tile lives only in LDS (csrc/kernels/stem_fused.hip).
 struct StemFusedParams {
-  int src;                  // 0 letterbox, 1 crop gather
+  int src;                  // 0 letterbox, 1 crop gather, 2 fp32 tensor
   const uint8_t* pool;
   const ImageMeta* meta;
   const Ctrl* ctrl;         // live counts (n_images / n_crops, crop_base)
@@ -471,7 +472,9 @@ struct StemFusedParams {
 };
 void stem_fused(const StemFusedParams& p, hipStream_t s);
 // fp32 detector front end (csrc/kernels/stem_x3.hip): letterbox -> stem -> 3x3 s2 conv with the stem map only in
-// LDS; w = pre-split stem planes / 255 [3 ky][2 slabs][16][3][32], w2 = pre-split [9 taps][32][3][16], y2 fp32
+// LDS; w = pre-split stem planes / 255 [3 ky][2 slabs][16][3][32], w2 = pre-split [9 taps][32][3][16], y2 fp32.
+// src 2 reads the request tensors instead of letterboxing (3 S^2 floats at pool + meta[b].offset; w without / 255).
+// ARENA_STEM_X3_TH / ARENA_STEM_X3_NW pick the <TH, NW> instantiation (4,4 default; 4,2; 8,4).
 void stem_s2_f32(const StemFusedParams& p, hipStream_t s);
 void stem_s2_f32_prepare();
 

@@ -19,6 +19,18 @@
 //      stride-2 fragment reads of 16 consecutive lanes hit consecutive LDS rows;
 //   4. + bias, SiLU, fp32 NHWC store.
 // Weights are read straight from global memory (L2-resident, 41 KB) into fragment registers at each GEMM's start.
+//
+// Tensor source (SRC 2: the yolov5n tensor model, FP32 NCHW [3, S, S] requests in the image pool).  Step 1 reads
+// the tile's s2d pixels straight from the request's three planes (the addressing of tensor_in_s2d_kernel<float>;
+// zero outside the map), so the S/2 x S/2 x 16 fp32 s2d map is never written.  A tensor holds arbitrary fp32
+// values, so the one-exact-plane trick of the letterbox source does not apply: the input is split into h | m | l
+// bf16 planes in LDS (three copies of the step-1 region) and the stem GEMM takes six partial products per operand
+// pair, the scheme of step 3; its weights carry no 1/255 (a separate pack in the planner).  Chosen over
+// v_mfma_f32_16x16x4_f32 on an fp32 LDS tile by code size: the bf16 form reuses step 2's fragment addressing,
+// weight layout and epilogue unchanged (one extra plane offset per read), where the fp32 instruction's 4-deep K
+// needs its own [k][px] tile layout, 36 K steps per fragment instead of 6 and an fp32 weight pack; the stem GEMM
+// is a sixth of the kernel's MFMA work either way.  Steps 3-4 are the letterbox source's, instruction for
+// instruction.
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
@@ -46,8 +58,9 @@ constexpr int SX_SP = 56;                   // bf16 per stem pixel: 3 planes x 1
 constexpr int SX_SRS = SX_SCS * SX_SP + 16; // bf16 per stored stem row
 
 __host__ __device__ constexpr int sx_sr(int TH) { return 2 * TH + 1; }  // stem rows per tile
-__host__ __device__ constexpr int sx_lds_bytes(int TH) {
-  return ((sx_sr(TH) + 2) * SX_IC * SX_IP + sx_sr(TH) * SX_SRS) * 2;
+__host__ __device__ constexpr int sx_in_planes(int SRC) { return SRC == 2 ? 3 : 1; }  // bf16 planes of the input
+__host__ __device__ constexpr int sx_lds_bytes(int TH, int SRC) {
+  return (sx_in_planes(SRC) * (sx_sr(TH) + 2) * SX_IC * SX_IP + sx_sr(TH) * SX_SRS) * 2;
 }
 
 __device__ __forceinline__ int sx_xcd_remap(int bx, int nx) {
@@ -57,17 +70,18 @@ __device__ __forceinline__ int sx_xcd_remap(int bx, int nx) {
 
 }  // namespace
 
-template <int TH, int NW>
+template <int TH, int NW, int SRC>
 __global__ __launch_bounds__(NW * 64) void stem_s2_x3_kernel(const StemFusedParams p) {
   constexpr int NT = NW * 64;
   constexpr int SR = sx_sr(TH), IR = SR + 2;
+  constexpr int IN_PL = IR * SX_IC * SX_IP;  // bf16 per input plane
   constexpr int NSP = SR * SX_SC;            // stem pixels of the tile
   constexpr int NSF = (NSP + 15) / 16;       // 16-pixel stem fragments
   constexpr int NOF = TH / 2;                // 32-pixel output fragments (2 rows x 16 columns)
   static_assert(TH % 2 == 0, "output fragments are two rows");
   extern __shared__ __attribute__((aligned(16))) bf16 sx_lds[];
-  bf16* sIn = sx_lds;                        // [IR][35][SX_IP]
-  bf16* sSt = sx_lds + IR * SX_IC * SX_IP;   // [SR][SX_SRS]: 34 pixels of SX_SP + pad
+  bf16* sIn = sx_lds;                        // [1 | 3 planes][IR][35][SX_IP]
+  bf16* sSt = sx_lds + sx_in_planes(SRC) * IN_PL;  // [SR][SX_SRS]: 34 pixels of SX_SP + pad
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int T2 = p.S / 2, Ho = p.S / 4, Wo = p.S / 4;  // s2d / stem map side, output side
@@ -84,8 +98,53 @@ __global__ __launch_bounds__(NW * 64) void stem_s2_x3_kernel(const StemFusedPara
 
   const int col = lane & 15, kq = lane >> 4, fr = lane & 31, fh = lane >> 5;
 
-  // ---- 1. letterboxed s2d input, uint8 values as one bf16 plane (zero outside the map: the stem's padding)
-  {
+  // ---- 1. (tensor source) s2d input from the request's fp32 NCHW planes, split into h | m | l bf16 planes
+  if constexpr (SRC == 2) {
+    constexpr int NPX = IR * SX_IC, PXT = (NPX + NT - 1) / NT;
+    const float* __restrict__ img = (const float*)(p.pool + p.meta[b].offset);
+    const size_t plane = (size_t)p.S * p.S;
+    // addresses of dead pixels are clamped to the map's origin and every load is issued unconditionally, so all
+    // 12 x PXT loads of a thread are in flight together; rows 2 iy, 2 iy + 1 < S and columns 2 ix, 2 ix + 1 < S
+    float v[PXT][12];
+    bool ok[PXT];
+#pragma unroll
+    for (int j = 0; j < PXT; ++j) {
+      const int px = tid + NT * j;
+      const int hy = px / SX_IC, hx = px - hy * SX_IC;
+      const int iy = iy0 + hy, ix = ix0 + hx;
+      ok[j] = px < NPX && (unsigned)iy < (unsigned)T2 && (unsigned)ix < (unsigned)T2;
+      const float* s = img + (ok[j] ? (size_t)(2 * iy) * p.S + 2 * ix : (size_t)0);
+#pragma unroll
+      for (int pq = 0; pq < 4; ++pq)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[j][pq * 3 + c] = s[c * plane + (size_t)(pq >> 1) * p.S + (pq & 1)];
+    }
+#pragma unroll
+    for (int j = 0; j < PXT; ++j) {
+      const int px = tid + NT * j;
+      if (px < NPX) {
+        bf16x8 h[2], m[2], l[2];
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+          const float x = c < 12 && ok[j] ? v[j][c] : 0.f;
+          const bf16 th = (bf16)x;
+          const float rr = x - (float)th;
+          const bf16 tm = (bf16)rr;
+          h[c >> 3][c & 7] = th;
+          m[c >> 3][c & 7] = tm;
+          l[c >> 3][c & 7] = (bf16)(rr - (float)tm);
+        }
+        bf16* d = sIn + px * SX_IP;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          *(bf16x8*)(d + 8 * q) = h[q];
+          *(bf16x8*)(d + IN_PL + 8 * q) = m[q];
+          *(bf16x8*)(d + 2 * IN_PL + 8 * q) = l[q];
+        }
+      }
+    }
+  } else {
+    // ---- 1. letterboxed s2d input, uint8 values as one bf16 plane (zero outside the map: the stem's padding)
     // every sample of this thread is issued before the first is stored: the byte loads of all PXT pixels are in
     // flight together (one pixel per pass waited out a global-load latency per pass)
     constexpr int NPX = IR * SX_IC, PXT = (NPX + NT - 1) / NT;
@@ -186,8 +245,19 @@ __global__ __launch_bounds__(NW * 64) void stem_s2_x3_kernel(const StemFusedPara
         for (int sl = 0; sl < 2; ++sl) {
           const int kabs = sl * 32 + kq * 8;
           const int kx = kabs >> 4 < 3 ? kabs >> 4 : 2, c0 = kabs & 15;  // kx 3: zero weights
-          const bf16x8 x = *(const bf16x8*)(sIn + ((sr + ky) * SX_IC + sc + kx) * SX_IP + c0);
+          const bf16* xa = sIn + ((sr + ky) * SX_IC + sc + kx) * SX_IP + c0;
+          const bf16x8 x = *(const bf16x8*)xa;
           const int s = ky * 2 + sl;
+          if constexpr (SRC == 2) {  // x = the h plane; six partial products, smallest first
+            const bf16x8 xm = *(const bf16x8*)(xa + IN_PL), xl = *(const bf16x8*)(xa + 2 * IN_PL);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[s], xm, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[s], x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[s], xl, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[s], x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[s], xm, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[s], x, acc, 0, 0, 0);
+            continue;
+          }
           acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[s], x, acc, 0, 0, 0);
           acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[s], x, acc, 0, 0, 0);
           acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[s], x, acc, 0, 0, 0);
@@ -290,43 +360,59 @@ __global__ __launch_bounds__(NW * 64) void stem_s2_x3_kernel(const StemFusedPara
 
 namespace {
 
-template <int TH, int NW>
+template <int TH, int NW, int SRC>
 void sx_launch(const StemFusedParams& p, hipStream_t s) {
   const int tiles = (p.S / 4 / TH) * (p.S / 4 / SX_TW);
-  hipLaunchKernelGGL((stem_s2_x3_kernel<TH, NW>), dim3((unsigned)(p.cap * tiles)), dim3(NW * 64), sx_lds_bytes(TH),
-                     s, p);
+  hipLaunchKernelGGL((stem_s2_x3_kernel<TH, NW, SRC>), dim3((unsigned)(p.cap * tiles)), dim3(NW * 64),
+                     sx_lds_bytes(TH, SRC), s, p);
+}
+
+template <int SRC>
+void sx_dispatch(const StemFusedParams& p, int th, int nw, hipStream_t s) {
+  if (th == 8)
+    sx_launch<8, 4, SRC>(p, s);
+  else if (nw == 2)
+    sx_launch<4, 2, SRC>(p, s);
+  else
+    sx_launch<4, 4, SRC>(p, s);
+}
+
+template <int TH, int NW, int SRC>
+void sx_prepare() {
+  static_assert(sx_lds_bytes(TH, SRC) <= 160 * 1024, "one workgroup's LDS on gfx950");
+  ARENA_HIP_CHECK(hipFuncSetAttribute((const void*)stem_s2_x3_kernel<TH, NW, SRC>,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, sx_lds_bytes(TH, SRC)));
 }
 
 }  // namespace
 
-// Geometry the kernel assumes (checked here, on the host, before any launch): letterbox source, 16 -> 16 stem,
+// Geometry the kernel assumes (checked here, on the host, before any launch): letterbox (0) or tensor (2) source
+// (the tensor source reads 3 S^2 floats from pool + meta[b].offset of every live image), 16 -> 16 stem,
 // 16 -> 32 stride-2 conv, output side S / 4 a multiple of the 16-wide tile and of TH, fp32 output with a
 // float4-aligned pixel stride.  STEM_X3_TH (4 default / 8) picks the tile height.
 void stem_s2_f32(const StemFusedParams& p, hipStream_t s) {
-  if (p.src != 0 || p.KS != 3 || p.Cout != 16 || p.w2 == nullptr || p.Cout2 != 32 || p.y2 == nullptr ||
+  if ((p.src != 0 && p.src != 2) || p.KS != 3 || p.Cout != 16 || p.w2 == nullptr || p.Cout2 != 32 || p.y2 == nullptr ||
       p.y2s % 4 != 0 || p.y2s < 32 || p.S % 64 != 0 || p.pool == nullptr || p.meta == nullptr)
-    throw std::runtime_error("stem_s2_f32: needs letterbox src, 3x3 16->16 stem, 3x3 s2 16->32, S % 64 == 0");
+    throw std::runtime_error("stem_s2_f32: needs letterbox or tensor src, 3x3 16->16 stem, 3x3 s2 16->32, S % 64 == 0");
   if (p.cap <= 0) return;
   // ARENA_STEM_X3_TH: tile rows (4 default, 8); ARENA_STEM_X3_NW: waves per workgroup (TH 4: 2 or 4; TH 8: 4)
   const char* e = std::getenv("ARENA_STEM_X3_TH");  // read per enqueue: graphs capture it once
   const char* n = std::getenv("ARENA_STEM_X3_NW");
   const int th = e != nullptr && std::atoi(e) == 8 ? 8 : 4;
   const int nw = n != nullptr ? std::atoi(n) : 4;
-  if (th == 8)
-    sx_launch<8, 4>(p, s);
-  else if (nw == 2)
-    sx_launch<4, 2>(p, s);
+  if (p.src == 2)
+    sx_dispatch<2>(p, th, nw, s);
   else
-    sx_launch<4, 4>(p, s);
+    sx_dispatch<0>(p, th, nw, s);
 }
 
 void stem_s2_f32_prepare() {
-  ARENA_HIP_CHECK(hipFuncSetAttribute((const void*)stem_s2_x3_kernel<4, 2>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, sx_lds_bytes(4)));
-  ARENA_HIP_CHECK(hipFuncSetAttribute((const void*)stem_s2_x3_kernel<4, 4>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, sx_lds_bytes(4)));
-  ARENA_HIP_CHECK(hipFuncSetAttribute((const void*)stem_s2_x3_kernel<8, 4>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, sx_lds_bytes(8)));
+  sx_prepare<4, 2, 0>();
+  sx_prepare<4, 4, 0>();
+  sx_prepare<8, 4, 0>();
+  sx_prepare<4, 2, 2>();
+  sx_prepare<4, 4, 2>();
+  sx_prepare<8, 4, 2>();
 }
 
 }  // namespace arena

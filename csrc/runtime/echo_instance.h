@@ -21,9 +21,13 @@ class EchoInstance : public BatchInstance {
  public:
   // latency_us: collect() returns no earlier than this long after submit (a stand-in for device time)
   // staging_cap: the staging_bytes() it reports (0 = unlimited), as an Executor reports its slot's image pool
-  EchoInstance(int slots, int max_batch, int max_det = 4, int latency_us = 0, int64_t staging_cap = 0)
+  // raw_out_bytes: > 0 makes it a raw-output (tensor model) instance: for an fp32 tensor input (bytes > 0) of
+  //   n_in floats, output float j of the item is in[(7 j) mod n_in] + (j mod 13), so a test can tell that every
+  //   answer belongs to its request; 0 (default): no raw output
+  EchoInstance(int slots, int max_batch, int max_det = 4, int latency_us = 0, int64_t staging_cap = 0,
+               int64_t raw_out_bytes = 0)
       : slots_(slots), max_batch_(max_batch), max_det_(max_det), latency_us_(latency_us), staging_cap_(staging_cap),
-        results_(slots),
+        raw_out_bytes_(raw_out_bytes), results_(slots),
         busy_(slots, false), t_submit_(slots) {}
   std::vector<int> buckets() const override {
     std::vector<int> b;
@@ -33,7 +37,7 @@ class EchoInstance : public BatchInstance {
   }
   int num_slots() const override { return slots_; }
   int max_det() const override { return max_det_; }
-  int64_t raw_out_bytes() const override { return 0; }
+  int64_t raw_out_bytes() const override { return raw_out_bytes_; }
   int64_t staging_bytes() const override { return staging_cap_; }
 
   // Image i of a batch gets min(max_det, 1 + first_byte % max_det) detections: box k spans
@@ -51,8 +55,19 @@ class EchoInstance : public BatchInstance {
     r.det_count.resize(n);
     r.det.resize((size_t)n * max_det_);
     r.crop_offset.resize(n + 1);
+    const size_t n_out = (size_t)raw_out_bytes_ / 4;
+    if (n_out > 0) r.raw.assign((size_t)n * n_out * 4, 0);
     int total = 0;
     for (int i = 0; i < n; ++i) {
+      const size_t n_in = imgs[i].bytes > 0 ? (size_t)imgs[i].bytes / 4 : 0;
+      if (n_out > 0 && n_in > 0) {
+        for (size_t j = 0; j < n_out; ++j) {
+          float v;
+          std::memcpy(&v, imgs[i].data + 4 * ((7 * j) % n_in), 4);
+          v += (float)(j % 13);
+          std::memcpy(r.raw.data() + ((size_t)i * n_out + j) * 4, &v, 4);
+        }
+      }
       uint8_t first = imgs[i].data[0];
       if (imgs[i].jpeg != nullptr) {  // split-decoded JPEG: reconstruct like the device would (host reference)
         std::vector<uint8_t> rgb((size_t)imgs[i].h * imgs[i].w * 3);
@@ -122,7 +137,7 @@ class EchoInstance : public BatchInstance {
 
  private:
   int slots_, max_batch_, max_det_, latency_us_;
-  int64_t staging_cap_;
+  int64_t staging_cap_, raw_out_bytes_;
   std::vector<BatchResult> results_;
   std::vector<bool> busy_;
   std::vector<std::chrono::steady_clock::time_point> t_submit_;

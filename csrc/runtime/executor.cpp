@@ -1018,7 +1018,7 @@ void Executor::enqueue_program(const std::vector<OpRecord>& prog, Bucket& bk, Sl
         p.meta = meta;
         p.ctrl = ctrl;
         if (f32)
-          stem_s2_f32(p, s);  // fp32: letterbox + stem + 3x3 s2 conv (the only fp32 stem_fused form)
+          stem_s2_f32(p, s);  // fp32: letterbox (src 0) or request tensor (src 2) + stem + 3x3 s2 conv
         else
           stem_fused(p, s);
         break;

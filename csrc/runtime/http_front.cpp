@@ -325,6 +325,16 @@ HttpFrontEnd::HttpFrontEnd(DynamicBatcher* batcher, DecodeChannel dc, std::vecto
     if (cfg_.decode_threads > 0)
       host_pool_ = HostBufferPool::create(cfg_.decode_buffer_cap, cfg_.host_alloc, cfg_.host_free);
   }
+  for (const TensorModelEntry& e : cfg_.tensor_models) {
+    if (e.batcher == nullptr || e.model.name.empty() || e.model.in_item_bytes() <= 0 || e.model.out_item_bytes() <= 0)
+      throw std::runtime_error("HttpFrontEnd: tensor model '" + e.model.name + "' needs a batcher and its dims");
+    if (e.model.name == cfg_.kserve_model)
+      throw std::runtime_error("HttpFrontEnd: tensor model '" + e.model.name + "' has the ensemble's name");
+    TensorModelStats ts;
+    ts.name = e.model.name;
+    stats_.tensor_models.push_back(ts);
+  }
+  bodies_.set_budget_slots((size_t)(std::max(1, cfg_.io_threads) + std::max(0, cfg_.body_pool_depth)));
   stats_.latency_hist.assign(kLatencyBucketsMs.size() + 1, 0);
   stats_.stage_hist.assign(kStages.size(), std::vector<int64_t>(kLatencyBucketsMs.size() + 1, 0));
   stats_.stage_sum_ms.assign(kStages.size(), 0.0);
@@ -499,6 +509,9 @@ FrontStats HttpFrontEnd::stats() {
   }
   s.bodies_recycled = (int64_t)bodies_.hits();
   s.bodies_allocated = (int64_t)bodies_.misses();
+  s.bodies_retained_bytes = (int64_t)bodies_.retained_bytes();
+  s.bodies_budget_bytes = (int64_t)bodies_.budget_bytes();
+  s.bodies_over_budget = (int64_t)bodies_.over_budget();
   return s;
 }
 
@@ -856,7 +869,7 @@ bool HttpFrontEnd::parse_one_impl(const std::shared_ptr<Conn>& c) {
 
 void HttpFrontEnd::dispatch(const std::shared_ptr<Conn>& c, const std::string& method, const std::string& path,
                             const std::string& ctype, std::string&& body, int64_t ihcl) {
-  if (!cfg_.kserve_model.empty() && path.rfind("/v2", 0) == 0 && kserve_route(c, method, path, std::move(body), ihcl))
+  if ((!cfg_.kserve_model.empty() || !cfg_.tensor_models.empty()) && path.rfind("/v2", 0) == 0 && kserve_route(c, method, path, std::move(body), ihcl))
     return;
   if (path == "/predict") {
     if (method != "POST") {
@@ -1000,17 +1013,38 @@ bool HttpFrontEnd::kserve_route(const std::shared_ptr<Conn>& c, const std::strin
                                 std::string&& body, int64_t ihcl) {
   const std::string& m = cfg_.kserve_model;
   const std::string mpre = "/v2/models/" + m;
+  const bool ens = !m.empty();  // tensor models alone: the ensemble's routes do not exist
   auto err_json = [](const std::string& msg) {
     std::string s = "{\"error\":";
     json_escape(s, msg);
     return s + "}";
   };
+  for (size_t k = 0; k < cfg_.tensor_models.size(); ++k) {
+    const KServeTensorModel& tm = cfg_.tensor_models[k].model;
+    const std::string pre = "/v2/models/" + tm.name;
+    if (path.compare(0, pre.size(), pre) != 0) continue;
+    std::string rest = path.substr(pre.size());
+    if (rest.compare(0, 11, "/versions/1") == 0 && (rest.size() == 11 || rest[11] == '/')) rest.erase(0, 11);
+    if (method == "GET" && rest.empty()) {
+      respond(c, 200, "application/json", kserve_tensor_model_metadata(tm));
+      return true;
+    }
+    if (method == "GET" && rest == "/ready") {
+      const bool ok = healthy_.load();
+      respond(c, ok ? 200 : 503, "application/json", ok ? "{\"ready\":true}" : "{\"ready\":false}");
+      return true;
+    }
+    if (method == "POST" && rest == "/infer") {
+      tensor_infer(c, k, std::move(body), ihcl);
+      return true;
+    }
+  }
   if (method == "GET") {
     if (path == "/v2/health/live") {
       respond(c, 200, "application/json", "{\"live\":true}");
       return true;
     }
-    if (path == "/v2/health/ready" || path == mpre + "/ready" || path == mpre + "/versions/1/ready") {
+    if (path == "/v2/health/ready" || (ens && (path == mpre + "/ready" || path == mpre + "/versions/1/ready"))) {
       const bool ok = healthy_.load();
       respond(c, ok ? 200 : 503, "application/json", ok ? "{\"ready\":true}" : "{\"ready\":false}");
       return true;
@@ -1020,14 +1054,14 @@ bool HttpFrontEnd::kserve_route(const std::shared_ptr<Conn>& c, const std::strin
               "{\"name\":\"arena-modelserver-native\",\"version\":\"2.0.0\",\"extensions\":[\"binary_tensor_data\"]}");
       return true;
     }
-    if (path == mpre || path == mpre + "/versions/1") {
+    if (ens && (path == mpre || path == mpre + "/versions/1")) {
       respond(c, 200, "application/json", kserve_model_metadata(m));
       return true;
     }
     return false;
   }
   if (method != "POST") return false;
-  const bool infer = path == mpre + "/infer" || path == mpre + "/versions/1/infer";
+  const bool infer = ens && (path == mpre + "/infer" || path == mpre + "/versions/1/infer");
   if (!infer) {
     if (path.size() > 6 && path.compare(path.size() - 6, 6, "/infer") == 0) {
       respond(c, 404, "application/json", err_json("Request for unknown model: '" + path + "' is not found"));
@@ -1049,6 +1083,124 @@ bool HttpFrontEnd::kserve_route(const std::shared_ptr<Conn>& c, const std::strin
   t_predict_dispatched = true;
   start_upload(c, t0, std::move(body), off, len, 1);
   return true;
+}
+
+// One tensor infer request in flight: the body (the items' storage: the batcher reads them in place), one result
+// per item, and the count of items still out.  Shared by the items' callbacks and, as their `owner`, by the
+// batcher; the last callback answers and hands the body back to the pool.
+struct HttpFrontEnd::TensorJob {
+  std::shared_ptr<Conn> conn;
+  Clock_tp t0;
+  size_t model = 0;
+  KServeTensorRequest req;
+  std::string body;
+  std::vector<RequestResult> results;
+  std::atomic<int64_t> left{0};
+  int reject = 0;  // 503 queue full / 413 beyond the staging capacity: set before the item counts as done
+};
+
+void HttpFrontEnd::tensor_infer(const std::shared_ptr<Conn>& c, size_t model, std::string&& body, int64_t ihcl) {
+  const TensorModelEntry& e = cfg_.tensor_models[model];
+  auto job = std::make_shared<TensorJob>();
+  job->conn = c;
+  job->t0 = Clock::now();
+  job->model = model;
+  auto reject = [&](int code, const std::string& msg) {
+    {
+      std::lock_guard<std::mutex> sl(stats_mu_);
+      TensorModelStats& ts = stats_.tensor_models[model];
+      ++ts.requests;
+      ++ts.failed;
+    }
+    bodies_.put(std::move(body));
+    fail_request(c, code, msg, 1);
+  };
+  if (!healthy_.load()) return reject(503, "Server not ready");
+  std::string err;
+  if (!kserve_parse_tensor_input(body, ihcl, e.model, job->req, err)) return reject(400, err);
+  t_predict_dispatched = true;
+  const int64_t n = job->req.n;
+  const int side = (int)e.model.in_item().back();
+  job->body = std::move(body);
+  job->results.resize((size_t)n);
+  job->left.store(n);
+  HttpFrontEnd* self = this;
+  for (int64_t i = 0; i < n; ++i) {
+    InputImage in{(const uint8_t*)job->body.data() + job->req.off + (size_t)(i * job->req.item_bytes), side, side};
+    in.bytes = job->req.item_bytes;
+    {
+      std::lock_guard<std::mutex> lk(cb_mu_);
+      ++cb_outstanding_;
+    }
+    const int64_t id = e.batcher->enqueue_input(in, job, [self, job, i](RequestResult&& r) {
+      struct Done {
+        HttpFrontEnd* f;
+        ~Done() { f->callback_done(); }
+      } done{self};
+      job->results[(size_t)i] = std::move(r);
+      self->tensor_item_done(job);
+    });
+    if (id >= 0) continue;
+    callback_done();  // rejected: the batcher never calls back, for this item or the ones not yet offered
+    job->reject = id == -2 ? 413 : 503;
+    for (int64_t k = i; k < n; ++k) tensor_item_done(job);
+    return;
+  }
+}
+
+void HttpFrontEnd::tensor_item_done(const std::shared_ptr<TensorJob>& job) {
+  if (job->left.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
+  // the last item: every result is in and no batch reads the body any more
+  const KServeTensorModel& tm = cfg_.tensor_models[job->model].model;
+  std::string error;
+  int code = 200;
+  if (job->reject != 0) {
+    code = job->reject;
+    error = code == 413 ? "input exceeds the staging capacity of one batch" : "request queue is full";
+  }
+  double queue_us = 0, compute_us = 0;
+  std::vector<const std::vector<uint8_t>*> items;
+  for (const RequestResult& r : job->results) {
+    if (code != 200) break;
+    if (!r.error.empty()) {
+      code = 500;
+      error = r.error;
+    } else if ((int64_t)r.raw.size() != tm.out_item_bytes()) {
+      code = 500;
+      error = "model '" + tm.name + "' returned " + std::to_string(r.raw.size()) + " output bytes, expected " +
+              std::to_string(tm.out_item_bytes());
+    }
+    queue_us += r.queue_us;
+    compute_us += r.compute_us;
+    items.push_back(&r.raw);
+  }
+  std::string body;
+  int64_t ihcl = -1;
+  if (code == 200) body = kserve_build_tensor_response(tm, job->req.id, job->req.batch_dim, items, &ihcl);
+  const double total_ms = ms_since(job->t0);
+  {
+    std::lock_guard<std::mutex> sl(stats_mu_);
+    TensorModelStats& ts = stats_.tensor_models[job->model];
+    ++ts.requests;
+    if (code == 200) {
+      ++ts.ok;
+      ts.items += job->req.n;
+      ts.request_us += total_ms * 1e3;
+      ts.queue_us += queue_us;
+      ts.compute_us += compute_us;
+    } else {
+      ++ts.failed;
+    }
+  }
+  bodies_.put(std::move(job->body));
+  if (code != 200) return fail_request(job->conn, code, error, 1);
+  {
+    std::lock_guard<std::mutex> sl(stats_mu_);
+    ++stats_.requests;
+    ++stats_.ok;
+  }
+  respond(job->conn, 200, "application/octet-stream", body, false,
+          "Inference-Header-Content-Length: " + std::to_string(ihcl) + "\r\n");
 }
 
 std::vector<int64_t> HttpFrontEnd::upstream_forwarded() const {

@@ -77,6 +77,13 @@ struct DecodeChannel {
   int result_fd = -1, result_wfd = -1;
 };
 
+// A tensor model served on the KServe routes next to the ensemble (runtime/kserve.h): its contract and the
+// dynamic batcher its requests go to (owned by the caller; it outlives the front end).
+struct TensorModelEntry {
+  KServeTensorModel model;
+  DynamicBatcher* batcher = nullptr;
+};
+
 struct FrontConfig {
   std::string host = "0.0.0.0";
   int port = 8100;
@@ -106,6 +113,14 @@ struct FrontConfig {
   // binary tensor extension takes the /predict path and answers the ensemble's output tensors; GET /v2,
   // /v2/health/{live,ready}, /v2/models/<m>[/ready] answer the protocol's metadata / health routes
   std::string kserve_model;
+  // Tensor models on the same routes: POST /v2/models/<name>[/versions/1]/infer with one FP32 input in the binary
+  // tensor extension, .../ready and the metadata route.  A request's N items go to the model's batcher straight
+  // from the request body (enqueue_input); the answer is written when all N results are in, in request order.
+  std::vector<TensorModelEntry> tensor_models;
+  // Request bodies that can be in flight beyond one per I/O thread (queued for decode or in a batch): with the
+  // I/O threads it sizes the body pool's byte budget, (io_threads + body_pool_depth) x the largest body seen
+  // (runtime/string_pool.h).  Tensor requests are 4.9 MB each; 1024 retained strings of that size were 5 GB.
+  int body_pool_depth = 64;
   // Native gateway ("proxy mode", upstream_port > 0): /predict uploads are forwarded to a model server's KServe
   // endpoint over upstream_conns keep-alive connections and its output tensors answered as the reference JSON;
   // no batcher or decoder in this process
@@ -124,6 +139,13 @@ struct HandlerRequest {
   std::string data;  // the multipart "file" field (or the raw body)
 };
 
+// Counters of one tensor model's native requests (the model server folds them into its ModelStats).
+struct TensorModelStats {
+  std::string name;
+  int64_t requests = 0, items = 0, ok = 0, failed = 0;  // items: batch items of the successful requests
+  double request_us = 0, queue_us = 0, compute_us = 0;   // of the successful requests; queue / compute per item
+};
+
 struct FrontStats {
   int64_t requests = 0, ok = 0, bad_request = 0, too_large = 0, unavailable = 0, errors = 0, not_found = 0;
   int64_t connections = 0, open_connections = 0, detections = 0, timeouts = 0;
@@ -131,6 +153,9 @@ struct FrontStats {
   int64_t oriented_decoded = 0;  // of native_decoded: uploads with an EXIF orientation other than 1
   int64_t progressive_decoded = 0;  // of native_decoded: progressive (SOF2) uploads
   int64_t bodies_recycled = 0, bodies_allocated = 0;  // request bodies served by the body pool / newly grown
+  int64_t bodies_retained_bytes = 0, bodies_budget_bytes = 0;  // capacity the pool holds now / may hold
+  int64_t bodies_over_budget = 0;                     // returned bodies freed because of the byte budget
+  std::vector<TensorModelStats> tensor_models;        // FrontConfig.tensor_models order
   double sum_total_ms = 0, sum_decode_ms = 0, sum_queue_ms = 0, sum_gpu_ms = 0;
   // host CPU time (thread CPU clock) of request stages, summed: HTTP + multipart parse on the I/O threads, the
   // native decode (marker parse + entropy decode), the JSON response built in the batcher callback
@@ -233,6 +258,9 @@ class HttpFrontEnd {
   void start_upload(const std::shared_ptr<Conn>& c, Clock_tp t0, std::string&& body, size_t off, size_t len,
                     int kind);
   void proxy_predict(const std::shared_ptr<Conn>& c, Clock_tp t0, std::string upload);
+  struct TensorJob;
+  void tensor_infer(const std::shared_ptr<Conn>& c, size_t model, std::string&& body, int64_t ihcl);
+  void tensor_item_done(const std::shared_ptr<TensorJob>& job);
   void record_ok(double total_ms, double decode_ms, double queue_ms, double gpu_ms, double det_ms, double cls_ms,
                  int64_t n_det, double json_cpu_ms);
   void respond(const std::shared_ptr<Conn>& c, int code, const std::string& ctype, const std::string& body,

@@ -10,6 +10,7 @@
 #include <sys/socket.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
@@ -153,10 +154,13 @@ struct TensorDesc {
   std::string name, datatype;
   std::vector<int64_t> shape;
   int64_t binary_size = -1;
+  bool has_data = false;  // a JSON "data" member (no binary extension for this tensor)
 };
 
 // the "inputs" / "outputs" array of a KServe message header
-bool parse_tensors(const std::string& hdr, const char* field, std::vector<TensorDesc>& out, std::string* id) {
+// `present` (optional): whether the field exists; with it an absent field is not an error
+bool parse_tensors(const std::string& hdr, const char* field, std::vector<TensorDesc>& out, std::string* id,
+                   bool* present = nullptr) {
   bool found = false, ok = true;
   const bool good = for_members(hdr, 0, [&](const std::string& key, size_t v0, size_t v1) {
     (void)v1;
@@ -174,12 +178,14 @@ bool parse_tensors(const std::string& hdr, const char* field, std::vector<Tensor
           for_members(hdr, a, [&](const std::string& pk, size_t p0, size_t p1) {
             if (pk == "binary_data_size") t.binary_size = as_int(hdr, p0, p1);
           });
+        else if (k == "data") t.has_data = true;
         (void)b;
       });
       out.push_back(std::move(t));
     });
   });
-  return good && found && ok;
+  if (present != nullptr) *present = found;
+  return good && ok && (found || present != nullptr);
 }
 
 void json_str(std::string& out, const std::string& s) {
@@ -379,6 +385,203 @@ std::string kserve_model_metadata(const std::string& model) {
        "{\"name\":\"CLASS_IDS\",\"datatype\":\"INT32\",\"shape\":[-1,5]},{\"name\":\"CLASS_LOGITS\",\"datatype\":"
        "\"FP32\",\"shape\":[-1,5]},{\"name\":\"CLASS_PROBS\",\"datatype\":\"FP32\",\"shape\":[-1,5]},"
        "{\"name\":\"STAGE_MS\",\"datatype\":\"FP32\",\"shape\":[4]}]}";
+  return s;
+}
+
+// ---------------------------------------------------------------- server side, tensor models
+namespace {
+
+std::vector<int64_t> item_dims(const std::vector<int64_t>& dims, int max_batch_size) {
+  if (max_batch_size > 0 || dims.empty()) return dims;
+  return std::vector<int64_t>(dims.begin() + 1, dims.end());
+}
+
+int64_t dims_bytes(const std::vector<int64_t>& d) {
+  int64_t n = 4;
+  for (int64_t v : d) n *= std::max<int64_t>(v, 0);
+  return n;
+}
+
+void json_shape(std::string& out, const std::vector<int64_t>& shape) {
+  out += '[';
+  for (size_t k = 0; k < shape.size(); ++k) out += (k ? "," : "") + std::to_string(shape[k]);
+  out += ']';
+}
+
+std::string shape_text(const std::vector<int64_t>& shape) {
+  std::string s;
+  json_shape(s, shape);
+  return s;
+}
+
+}  // namespace
+
+std::vector<int64_t> KServeTensorModel::in_item() const { return item_dims(in_dims, max_batch_size); }
+std::vector<int64_t> KServeTensorModel::out_item() const { return item_dims(out_dims, max_batch_size); }
+int64_t KServeTensorModel::in_item_bytes() const { return dims_bytes(in_item()); }
+int64_t KServeTensorModel::out_item_bytes() const { return dims_bytes(out_item()); }
+
+bool kserve_parse_tensor_input(const std::string& body, int64_t ihcl, const KServeTensorModel& m,
+                               KServeTensorRequest& req, std::string& err) {
+  const std::string ext = "input '" + m.input +
+                          "' must use the binary tensor data extension (Inference-Header-Content-Length and "
+                          "parameters.binary_data_size); JSON \"data\" arrays are not served here";
+  if (ihcl < 0) {
+    err = ext;
+    return false;
+  }
+  if ((uint64_t)ihcl > body.size()) {
+    err = "Inference-Header-Content-Length exceeds the request body";
+    return false;
+  }
+  const std::string hdr = body.substr(0, (size_t)ihcl);
+  std::vector<TensorDesc> ins, outs;
+  req = KServeTensorRequest{};
+  if (!parse_tensors(hdr, "inputs", ins, &req.id)) {
+    err = "malformed inference request header";
+    return false;
+  }
+  if (ins.size() != 1) {
+    err = "model '" + m.name + "' takes exactly one input, got " + std::to_string(ins.size());
+    return false;
+  }
+  const TensorDesc& t = ins[0];
+  if (t.name != m.input) {
+    err = "expected input '" + m.input + "' for model '" + m.name + "', got '" + t.name + "'";
+    return false;
+  }
+  if (t.datatype != "FP32") {
+    err = "input '" + m.input + "': expected FP32, got " + (t.datatype.empty() ? "no datatype" : t.datatype);
+    return false;
+  }
+  const std::vector<int64_t> item = m.in_item();
+  const size_t r = item.size();
+  const bool batch_dim = t.shape.size() == r + 1;
+  if ((t.shape.size() != r && !batch_dim) ||
+      !std::equal(item.begin(), item.end(), t.shape.end() - (std::ptrdiff_t)r)) {
+    err = "input '" + m.input + "': unexpected shape " + shape_text(t.shape) + ", expected [" +
+          (m.max_batch_size > 0 ? "N," : "1,") + shape_text(item).substr(1);
+    return false;
+  }
+  const int64_t n = batch_dim ? t.shape[0] : 1;
+  const int64_t limit = m.max_batch_size > 0 ? m.max_batch_size : 1;
+  if (n < 1 || n > limit) {
+    err = "batch " + std::to_string(n) + " exceeds max_batch_size " + std::to_string(m.max_batch_size);
+    return false;
+  }
+  if (t.has_data || t.binary_size == -1) {
+    err = ext;
+    return false;
+  }
+  const int64_t item_bytes = dims_bytes(item);  // the model's own dims: no client number enters the product
+  if (item_bytes <= 0 || t.binary_size != n * item_bytes) {
+    err = "input '" + m.input + "': binary_data_size " + std::to_string(t.binary_size) + " does not match shape " +
+          shape_text(t.shape) + " (" + std::to_string(n * item_bytes) + " bytes)";
+    return false;
+  }
+  if ((uint64_t)t.binary_size > body.size() - (size_t)ihcl) {
+    err = "input '" + m.input + "': binary_data_size exceeds the request body";
+    return false;
+  }
+  bool have_outs = false;
+  if (!parse_tensors(hdr, "outputs", outs, nullptr, &have_outs)) {
+    err = "malformed inference request header";
+    return false;
+  }
+  for (const TensorDesc& o : outs)
+    if (o.name != m.output) {
+      err = "unexpected output '" + o.name + "' for model '" + m.name + "' (it has '" + m.output + "')";
+      return false;
+    }
+  req.off = (size_t)ihcl;
+  req.n = n;
+  req.item_bytes = item_bytes;
+  req.batch_dim = batch_dim;
+  return true;
+}
+
+std::string kserve_build_tensor_response(const KServeTensorModel& m, const std::string& id, bool batch_dim,
+                                         const std::vector<const std::vector<uint8_t>*>& items, int64_t* ihcl) {
+  const size_t item_bytes = (size_t)m.out_item_bytes();
+  for (const auto* it : items)
+    if (it == nullptr || it->size() != item_bytes)
+      throw std::invalid_argument("kserve_build_tensor_response: an item is not the model's output size");
+  if (items.empty() || (!batch_dim && items.size() != 1))
+    throw std::invalid_argument("kserve_build_tensor_response: item count does not fit the response shape");
+  std::vector<int64_t> shape = m.out_item();
+  if (batch_dim) shape.insert(shape.begin(), (int64_t)items.size());
+  std::string h = "{\"model_name\":";
+  json_str(h, m.name);
+  h += ",\"model_version\":\"1\",\"id\":";
+  json_str(h, id);
+  h += ",\"outputs\":[{\"name\":";
+  json_str(h, m.output);
+  h += ",\"datatype\":\"FP32\",\"shape\":";
+  json_shape(h, shape);
+  h += ",\"parameters\":{\"binary_data_size\":" + std::to_string(items.size() * item_bytes) + "}}]}";
+  *ihcl = (int64_t)h.size();
+  h.reserve(h.size() + items.size() * item_bytes);
+  for (const auto* it : items) h.append((const char*)it->data(), it->size());
+  return h;
+}
+
+bool kserve_parse_tensor_response(const std::string& body, int64_t ihcl, std::string& name,
+                                  std::vector<int64_t>& shape, size_t& off, size_t& len, std::string& err) {
+  if (ihcl < 0 || (uint64_t)ihcl > body.size()) {
+    err = "tensor response without a binary output";
+    return false;
+  }
+  std::vector<TensorDesc> outs;
+  if (!parse_tensors(body.substr(0, (size_t)ihcl), "outputs", outs, nullptr) || outs.size() != 1) {
+    err = "malformed inference response header";
+    return false;
+  }
+  const TensorDesc& t = outs[0];
+  const uint64_t avail = body.size() - (size_t)ihcl;
+  uint64_t n = 4;
+  for (int64_t d : t.shape) {
+    if (d < 0 || (d > 0 && n > UINT64_MAX / (uint64_t)d)) {  // the product must not wrap around
+      err = "output shape does not fit the response body";
+      return false;
+    }
+    n *= (uint64_t)d;
+  }
+  if (t.datatype != "FP32" || t.binary_size < 0 || (uint64_t)t.binary_size != n || n > avail) {
+    err = "output '" + t.name + "': datatype, shape and binary_data_size do not agree with the body";
+    return false;
+  }
+  name = t.name;
+  shape = t.shape;
+  off = (size_t)ihcl;
+  len = (size_t)n;
+  return true;
+}
+
+std::string kserve_tensor_model_metadata(const KServeTensorModel& m) {
+  auto tensor = [&](std::string& s, const std::string& name, const std::vector<int64_t>& dims) {
+    s += "{\"name\":";
+    json_str(s, name);
+    s += ",\"datatype\":\"FP32\",\"shape\":";
+    std::vector<int64_t> shape = dims;
+    if (m.max_batch_size > 0) shape.insert(shape.begin(), -1);
+    json_shape(s, shape);
+    s += '}';
+  };
+  std::string s = "{\"name\":";
+  json_str(s, m.name);
+  s += ",\"versions\":[";
+  if (m.versions.empty()) s += "\"1\"";
+  for (size_t k = 0; k < m.versions.size(); ++k) {
+    if (k) s += ',';
+    json_str(s, m.versions[k]);
+  }
+  s += "],\"platform\":";
+  json_str(s, m.platform);
+  s += ",\"inputs\":[";
+  tensor(s, m.input, m.in_dims);
+  s += "],\"outputs\":[";
+  tensor(s, m.output, m.out_dims);
+  s += "]}";
   return s;
 }
 

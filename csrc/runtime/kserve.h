@@ -8,6 +8,14 @@
 //     the upload takes the /predict path (split decoder, dynamic batcher, device program) and the answer is the
 //     ensemble's outputs DETECTIONS [n,6] FP32, CLASS_IDS [n,5] INT32, CLASS_LOGITS / CLASS_PROBS [n,5] FP32,
 //     STAGE_MS [4] FP32 as binary tensors (JSON "data" arrays when the request carried no binary extension);
+//   server side, tensor models (FrontConfig.tensor_models; the reference gateway's call pattern: one FP32
+//     [1,3,640,640] ModelInfer to `yolov5n`, then one FP32 [1,3,224,224] per crop to `mobilenetv2`): the same
+//     route for each registered model, with a JSON header naming exactly one FP32 input [3,S,S] or [N,3,S,S]
+//     (1 <= N <= max_batch_size; N = 1 when that is 0) whose parameters.binary_data_size = product(shape) * 4 raw
+//     little-endian bytes follow the header.  The N items go to the model's dynamic batcher straight from the
+//     request body (enqueue_input, no copy) and the answer is the model's one output as a binary FP32 tensor,
+//     [N, ...] when the request had a batch dimension, else the item shape.  An input sent as a JSON "data" array
+//     is answered 400: a 1.2M-element JSON array is not a serving path.
 //   client side (KServeProxy, the native gateway): a pool of keep-alive connections that forward /predict
 //     uploads that way and turn the binary outputs back into a RequestResult for the reference JSON.
 //
@@ -48,6 +56,47 @@ bool kserve_parse_response(const std::string& body, int64_t ihcl, RequestResult&
 
 // Model metadata JSON of the ensemble (GET /v2/models/<model>).
 std::string kserve_model_metadata(const std::string& model);
+
+// A tensor model of the reference contract: one FP32 input -> one FP32 output, dims as in its config.pbtxt
+// (with max_batch_size 0 the dims carry the batch dimension themselves: [1,3,S,S]).
+struct KServeTensorModel {
+  std::string name, platform = "arena_hip";
+  std::vector<std::string> versions;   // metadata (empty: ["1"])
+  std::string input, output;
+  std::vector<int64_t> in_dims, out_dims;
+  int max_batch_size = 0;
+  // shape of one batch item: the dims, without their leading dimension when max_batch_size is 0
+  std::vector<int64_t> in_item() const;
+  std::vector<int64_t> out_item() const;
+  int64_t in_item_bytes() const;
+  int64_t out_item_bytes() const;
+};
+
+struct KServeTensorRequest {
+  std::string id;
+  size_t off = 0;          // first item's bytes inside the body; item i at off + i * item_bytes
+  int64_t n = 0;           // items
+  int64_t item_bytes = 0;
+  bool batch_dim = false;  // the request's shape had the leading N
+};
+
+// Request body -> the items of model `m`'s input inside `body` (binary tensor extension only).  `ihcl` as above.
+bool kserve_parse_tensor_input(const std::string& body, int64_t ihcl, const KServeTensorModel& m,
+                               KServeTensorRequest& req, std::string& err);
+
+// {"model_name", "model_version":"1", "id", "outputs":[{name, "datatype":"FP32", shape, "parameters":
+// {"binary_data_size"}}]} + the items' bytes in order (each copied once); *ihcl = header length.  Every item
+// must hold m.out_item_bytes() bytes (std::invalid_argument otherwise).
+std::string kserve_build_tensor_response(const KServeTensorModel& m, const std::string& id, bool batch_dim,
+                                         const std::vector<const std::vector<uint8_t>*>& items, int64_t* ihcl);
+
+// A tensor response -> its one output's name, shape and byte range inside `body`.
+bool kserve_parse_tensor_response(const std::string& body, int64_t ihcl, std::string& name,
+                                  std::vector<int64_t>& shape, size_t& off, size_t& len, std::string& err);
+
+// Metadata JSON of a tensor model: name, versions, platform, inputs / outputs {name, datatype, shape} with a
+// leading -1 when the model batches (the model server's ModelHandle.metadata()).
+std::string kserve_tensor_model_metadata(const KServeTensorModel& m);
 
 struct ProxyReply {
   int status = 0;          // upstream HTTP status (0: no answer)

@@ -115,7 +115,7 @@ class GpuProgramRunner:
         for B in self.buckets:
             cc = self.ex.crop_cap_for(B)
             validate_program(program, B, cc, max_det=self.max_det, cand_cap=int(program.meta.get("cand_cap", 8400)),
-                             raw_out_bytes=self.raw_out_bytes)
+                             raw_out_bytes=self.raw_out_bytes, pool_bytes_per_image=int(pool_bytes_per_image))
             offs, total = layout(program.buffers, B, cc, share=share_buffers)
             self._add_bucket(B, offs, total)
             self.arena_bytes[B] = total

@@ -43,7 +43,7 @@ Op record layouts (index: field) — keep in sync with executor.cpp:
            37-39 inv_std (float bits) 40 stem w_off 41 stem b_off
            (fused MobileNetV2 inverted residual, csrc/kernels/ir_block.hip / ir_f32.hip; stem = 1: fp32 crop
             gather + s2d stem conv computed inside the block-1 kernel, x_buf unused)
-  STEMFUSED 1 src (0 letterbox, 1 crop gather) 2 y_buf 3 y_coff 4 y_cs 5 S 6 w_off 7 Kpad 8 b_off
+  STEMFUSED 1 src (0 letterbox, 1 crop gather, 2 fp32 [3,S,S] pool tensors: fp32 programs) 2 y_buf 3 y_coff 4 y_cs 5 S 6 w_off 7 Kpad 8 b_off
            9 Cout 10 act 11 crops_buf 12-14 mean 15-17 inv_std (float bits) 18 batch_kind 19 KS
            20 second-conv flag 21 w2_off 22 Kpad2 23 b2_off 24 Cout2 25 act2 (y = the second conv's output)
            26 first-IR-block flag 27 wd_off 28 bd_off 29 wp_off 30 bp_off 31 oup (y = the block's output)
@@ -227,12 +227,13 @@ def pack_pw_weight_x3(w2: torch.Tensor, k2: int) -> bytes:
     return bf16_raw_bytes(planes.contiguous())
 
 
-def pack_stem_s2_x3(w0: torch.Tensor, w1: torch.Tensor) -> tuple[bytes, bytes]:
+def pack_stem_s2_x3(w0: torch.Tensor, w1: torch.Tensor, tensor_src: bool = False) -> tuple[bytes, bytes]:
     """fp32 detector front end (csrc/kernels/stem_x3.hip): the s2d stem weights [16, 16, 3, 3] divided by 255
     (the kernel stages the letterboxed uint8 values k) as bf16 planes [3 ky][2 slabs][16 ch][h|m|l][32 k]
     (slab k = kx * 16 + c for k < 48, zero for 48..63), and the 3x3 s2 conv [32, 16, 3, 3] as
-    [9 taps][32 ch][h|m|l][16 c]."""
-    w0 = w0.detach().float() / 255.0
+    [9 taps][32 ch][h|m|l][16 c].  ``tensor_src``: the kernel stages the request's own fp32 values (as three
+    bf16 planes), so the stem weights carry no 1/255."""
+    w0 = w0.detach().float() if tensor_src else w0.detach().float() / 255.0
     k = torch.zeros(16, 3, 64)
     k[:, :, :48] = w0.permute(0, 2, 3, 1).reshape(16, 3, 48)  # [n][ky][kx * 16 + c]
     p0 = split_bf16x3(k.reshape(16, 3, 2, 32))  # [n][ky][sl][3][32]
@@ -601,9 +602,12 @@ class ProgramBuilder:
 
     def stem_fused(self, dst: View, w: torch.Tensor, b: torch.Tensor, *, S: int, act: str, crops: Buffer | None = None,
                    mean=None, std=None, kind: int = IMAGES, second: tuple | None = None,
-                   ir: tuple | None = None) -> None:
+                   ir: tuple | None = None, tensor: bool = False) -> None:
         """Letterbox (``crops=None``) or crop gather + normalisation, fused with the s2d stem conv
         (``w``: [Cout, 16, KS, KS] over the space-to-depth input, pad top/left 1).
+
+        ``tensor=True`` (fp32 detector form only): the input is the request's fp32 NCHW [3, S, S] tensor in
+        the image pool instead of a letterboxed image (the tensor models' contract; src 2).
 
         ``second=(w2, b2, act2)`` (detector only): the following 3x3 stride-2 conv runs in the same
         kernel on the stem output kept in LDS; ``dst`` is then that conv's output (S/4 x S/4).
@@ -611,6 +615,8 @@ class ProgramBuilder:
         residual) runs on the stem output in LDS; ``dst`` is then the block's output (S/2 x S/2 x 16)."""
         if self.f32 and (second is None or crops is not None or ir is not None):
             raise ValueError("stem_fused: the fp32 form is letterbox + stem + 3x3 s2 conv (csrc/kernels/stem_x3.hip)")
+        if tensor and not self.f32:
+            raise ValueError("stem_fused: the tensor source is an fp32-program form (bf16 programs use tensor_in)")
         cout, cin, ks, ks2 = w.shape
         if cin != 16 or ks != ks2:
             raise ValueError("stem_fused: weights must be [Cout, 16, KS, KS]")
@@ -620,10 +626,10 @@ class ProgramBuilder:
         if self.f32:
             if (cout, ks, second[0].shape) != (16, 3, (32, 16, 3, 3)):
                 raise ValueError("stem_fused: the fp32 kernel takes a 3x3 16 -> 16 stem and a 3x3 s2 16 -> 32 conv")
-            wb, wb2_x3 = pack_stem_s2_x3(w, second[0])
+            wb, wb2_x3 = pack_stem_s2_x3(w, second[0], tensor_src=tensor)
         w_off = self.weights.add(wb)
         b_off = self.weights.add(bb)
-        src = 0 if crops is None else 1
+        src = 2 if tensor else 0 if crops is None else 1
         mean = mean if mean is not None else (0.0, 0.0, 0.0)
         std = std if std is not None else (1.0, 1.0, 1.0)
         if second is not None:

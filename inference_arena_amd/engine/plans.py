@@ -161,10 +161,14 @@ def plan_yolo(pb: ProgramBuilder, y: YOLOv5nu, T: int = 640, tensor_input: bool 
     w, b = fold(y.b0)
     if fuse_stem is None:
         fuse_stem = fuse_stem_default()
-    # fp32: only the letterbox + stem + s2 conv form exists (csrc/kernels/stem_x3.hip, ARENA_F32_STEM_S2)
+    # fp32: only the letterbox / tensor + stem + s2 conv form exists (csrc/kernels/stem_x3.hip, ARENA_F32_STEM_S2)
     fuse_stem = fuse_stem and (not pb.f32 or fuse_stem_s2_f32_default())
     A1 = pb.tensor("b1", h // 2, h // 2, 32)
-    if fuse_stem and not tensor_input and (fuse_stem2_default() or pb.f32) and T % 64 == 0:
+    if fuse_stem and tensor_input and pb.f32 and T % 64 == 0:
+        # request tensor + stem + b1 in one kernel: neither the s2d input nor the stem output is stored
+        w1, b1 = fold(y.b1)
+        pb.stem_fused(View(A1, 0, 32), s2d_stem_6x6(w), b, S=T, act="silu", second=(w1, b1, "silu"), tensor=True)
+    elif fuse_stem and not tensor_input and (fuse_stem2_default() or pb.f32) and T % 64 == 0:
         # letterbox + stem + b1 (3x3 s2) in one kernel: the 320x320x16 stem output stays in LDS
         w1, b1 = fold(y.b1)
         pb.stem_fused(View(A1, 0, 32), s2d_stem_6x6(w), b, S=T, act="silu", second=(w1, b1, "silu"))

@@ -87,7 +87,9 @@ def ir_crop_f32_supported(H: int, stride: int, inp_pad: int, hid_pad: int, oup_p
 
 
 def validate_program(prog: Program, B: int, crop_cap: int, *, max_det: int, cand_cap: int,
-                     raw_out_bytes: int | None = None) -> None:
+                     raw_out_bytes: int | None = None, pool_bytes_per_image: int | None = None) -> None:
+    """Static bounds / geometry check of every op.  ``pool_bytes_per_image``: the executor's image pool per batch
+    item, checked against ops that read request tensors from it (None: unknown, not checked)."""
     sizes = {}
     for b in prog.buffers:
         sizes[b.id] = b.per_item * (crop_cap if b.kind == CROPS else B)
@@ -254,13 +256,19 @@ def validate_program(prog: Program, B: int, crop_cap: int, *, max_det: int, cand
         elif op == OP_STEMFUSED:
             src, S, kpad, cout, kind, ks = int(r[1]), int(r[5]), int(r[7]), int(r[9]), int(r[18]), int(r[19])
             n = kind_n(kind)
-            expect = {0: (3, 16, 160, 0), 1: (2, 32, 64, CROPS)}.get(src)
+            expect = {0: (3, 16, 160, 0), 1: (2, 32, 64, CROPS), 2: (3, 16, 160, 0)}.get(src)
             if expect is None or (ks, cout, kpad, kind) != expect or S % 2:
                 raise ProgramError(f"op {i}: bad stem_fused geometry (src {src}, KS {ks}, Cout {cout}, Kpad {kpad})")
             if f32 and not int(r[20]):
                 raise ProgramError(f"op {i}: an fp32 stem_fused op must carry the fused second conv")
+            if src == 2:  # request tensors: fp32 [3, S, S] per item in the image pool (stem_x3.hip)
+                if not f32:
+                    raise ProgramError(f"op {i}: the tensor-source stem_fused op is an fp32-program op")
+                if pool_bytes_per_image is not None and pool_bytes_per_image < 3 * S * S * 4:
+                    raise ProgramError(f"op {i}: tensor-source stem reads {3 * S * S * 4} pool bytes per item, "
+                                       f"have {pool_bytes_per_image}")
             if int(r[20]):  # second conv fused: 3x3 s2 16 -> 32, output S/4
-                if src != 0 or int(r[24]) != 32 or int(r[22]) != 160 or S % 64:
+                if src not in (0, 2) or int(r[24]) != 32 or int(r[22]) != 160 or S % 64:
                     raise ProgramError(f"op {i}: bad fused second conv (Cout2 {int(r[24])}, Kpad2 {int(r[22])})")
                 view(i, r[2], int(r[3]), int(r[4]), n * (S // 4) ** 2, 32, el, "stem second-conv output")
                 # fp32 (stem_x3.hip): pre-split planes [9 taps][32][3][16]; bf16: [32][160]
@@ -277,7 +285,7 @@ def validate_program(prog: Program, B: int, crop_cap: int, *, max_det: int, cand
                 view(i, r[2], int(r[3]), int(r[4]), n * (S // 2) ** 2, cout, 2, "stem output")
             if src == 1:
                 need(i, r[11], 0, B * max_det * CROP_BYTES, "crop refs")
-            # fp32: pre-split planes / 255 [3 ky][2 slabs][16][3][32]; bf16: [Cout][Kpad]
+            # fp32: pre-split planes (/ 255 for src 0) [3 ky][2 slabs][16][3][32]; bf16: [Cout][Kpad]
             weights(i, int(r[6]), 3 * 2 * 16 * 3 * 32 * 2 if f32 else cout * kpad * 2, "stem weight")
             weights(i, int(r[8]), cout * 4, "stem bias")
         elif op == OP_ZERO:

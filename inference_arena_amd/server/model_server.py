@@ -322,17 +322,39 @@ def start_native_kserve(server: ModelServer, host_ip: str, port: int, model: str
     from ..labels import load_labels
     from .native_front import NativeFrontEnd
 
+    # every loaded tensor model with a native batcher is served on the same port (the reference gateway's call
+    # pattern: FP32 tensors to `yolov5n`, then to `mobilenetv2`); the Python servicers share the same batchers
+    tensor = [t for t in (native_tensor_entry(tm) for n, tm in server.models.items() if n != model) if t is not None]
     plan = (host or {}).get("plan") or {"http_io": int(os.environ.get("ARENA_HTTP_THREADS", "4")),
                                          "decode_threads": int(os.environ.get("ARENA_DECODE_THREADS", "8"))}
     fe = NativeFrontEnd(batcher, load_labels(None), port=port, host=host_ip, arch="triton",
                         io_threads=plan["http_io"], decode_threads=plan["decode_threads"],
                         decode_procs=int(os.environ.get("ARENA_DECODE_PROCS", "1") or 1), kserve_model=model,
+                        tensor_models=tensor,
                         gpu=str((host or {}).get("gpu", 0)), jpeg_device=server.device == "gpu")
+    for t in tensor:
+        # native requests never enter Python: their counters reach ModelStats (render_metrics, the statistics
+        # routes) when it is read
+        server.models[t["name"]].attach_native_stats(lambda name=t["name"]: fe.stats()["tensor_models"][name])
     if host:
         from ..parallel.affinity import rank_info_metrics
 
         fe.extra_metrics = rank_info_metrics(dict(host, plan=plan), "triton")
     return fe
+
+
+def native_tensor_entry(m) -> dict | None:
+    """A tensor model's entry for ``NativeFrontEnd(tensor_models=...)``: its contract as config.pbtxt states it
+    and its native dynamic batcher; None for a model that is no tensor model or has no native batcher."""
+    batcher = getattr(getattr(m, "batcher", None), "_b", None)
+    cfg = getattr(m, "config", None)
+    if batcher is None or cfg is None or not hasattr(m, "in_name") or len(cfg.input) != 1 or len(cfg.output) != 1:
+        return None
+    meta = m.metadata()
+    return {"name": m.name, "input": m.in_name, "in_dims": [int(d) for d in cfg.input[0].dims],
+            "output": m.out_name, "out_dims": [int(d) for d in cfg.output[0].dims],
+            "max_batch_size": int(cfg.max_batch_size), "platform": meta["platform"], "versions": meta["versions"],
+            "batcher": batcher}
 
 
 async def serve(args) -> None:

@@ -80,8 +80,40 @@ class ModelHandle:
         self.name = entry.name
         self.config = entry.config
         self.version = str(entry.versions[-1]) if entry.versions else "1"
-        self.stats = ModelStats()
+        self._stats = ModelStats()
+        self._native_source = None  # counters of the native endpoint's requests for this model
+        self._native_seen: dict = {}
         self.ready = False
+
+    @property
+    def stats(self) -> ModelStats:
+        """The model's counters; requests served by the native KServe endpoint (which never enter Python) are
+        folded in here, on every read, from the front end's own per-model counters."""
+        if self._native_source is not None:
+            self._fold_native()
+        return self._stats
+
+    def attach_native_stats(self, source) -> None:
+        """``source()``: the native front end's cumulative counters for this model (``requests, items, ok, failed,
+        request_us, queue_us, compute_us``; csrc/runtime/http_front.h TensorModelStats)."""
+        self._native_seen = dict(source())
+        self._native_source = source
+
+    def _fold_native(self) -> None:
+        st = self._stats
+        with st.lock:
+            cur = dict(self._native_source())
+            d = {k: cur.get(k, 0) - self._native_seen.get(k, 0) for k in cur}
+            self._native_seen = cur
+            if d.get("ok", 0) or d.get("failed", 0):
+                st.success += int(d.get("ok", 0))
+                st.failure += int(d.get("failed", 0))
+                st.inference_count += int(d.get("items", 0))
+                st.execution_count += int(d.get("ok", 0))
+                st.request_us += d.get("request_us", 0.0)
+                st.queue_us += d.get("queue_us", 0.0)
+                st.compute_us += d.get("compute_us", 0.0)
+                st.last_inference_ms = int(time.time() * 1e3)
 
     def metadata(self) -> dict:
         def t(x):

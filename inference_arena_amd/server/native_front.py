@@ -98,13 +98,17 @@ class NativeFrontEnd:
     def __init__(self, batcher, labels: list[str], *, port: int = 8100, host: str = "0.0.0.0",
                  io_threads: int = 4, decode_procs: int = 2, slots: int = 512, softmax: bool = False,
                  arch: str = "monolithic", gpu: str = "0", replica_tag: str = "", decode_threads: int = 8,
-                 jpeg_device: bool = True, kserve_model: str = "", progressive: bool | None = None, **http: int):
+                 jpeg_device: bool = True, kserve_model: str = "", progressive: bool | None = None,
+                 tensor_models: list[dict] | None = None, **http: int):
         """``decode_threads``: native split-decoder threads (0: every upload to the ``decode_procs`` PIL
         processes, the round-3 path); ``jpeg_device=False`` reconstructs on the host threads instead of the GPU
         (instances without the device half, e.g. the host-only EchoInstance, take either).  ``progressive``:
         progressive JPEG uploads take the split decoder too (None = Settings.ARENA_JPEG_PROGRESSIVE).  ``http``: further
         FrontConfig fields (max_body, idle_timeout_ms, read_timeout_ms; defaults from ARENA_HTTP_IDLE_TIMEOUT_MS
-        / ARENA_HTTP_READ_TIMEOUT_MS, else csrc/runtime/http_front.h)."""
+        / ARENA_HTTP_READ_TIMEOUT_MS, else csrc/runtime/http_front.h).  ``tensor_models``: tensor models served on
+        the KServe routes of the same port (csrc/runtime/kserve.h), each a dict ``{name, input, in_dims, output,
+        out_dims, max_batch_size, platform, versions, batcher}`` with the model's native DynamicBatcher; their
+        counters are ``stats()["tensor_models"][name]``."""
         from ..ops import native
         from ..processing.transforms import max_image_pixels
         from ..utils.settings import get_settings
@@ -120,6 +124,7 @@ class NativeFrontEnd:
                                          "max_image_pixels": int(max_image_pixels()),
                                          "progressive": bool(progressive),
                                          "kserve_model": str(kserve_model),
+                                         "tensor_models": [dict(t) for t in (tensor_models or [])],
                                          **_http_timeouts(), **{k: int(v) for k, v in http.items()}})
         self.registry = CollectorRegistry()
         self.registry.register(_Collector(self, arch, gpu))

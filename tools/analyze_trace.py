@@ -43,7 +43,8 @@ def describe(rec) -> str:
         return (f"c3 {int(rec[4])}x{int(rec[5])}x{int(rec[6])} c_={int(rec[7])} n={int(rec[8])}"
                 f"{' res' if rec[9] else ''}")
     if t == 15:
-        d = f"{'letterbox' if rec[1] == 0 else 'crop gather'} + stem k{int(rec[19])} -> {int(rec[9])}"
+        src = {0: "letterbox", 1: "crop gather", 2: "tensor"}.get(int(rec[1]), "?")
+        d = f"{src} + stem k{int(rec[19])} -> {int(rec[9])}"
         return d + (f" + k3 s2 -> {int(rec[24])}" if int(rec[20]) else "") + \
             (f" + ir t1 -> {int(rec[31])}" if int(rec[26]) else "")
     if t == 14 and int(rec[31]):
