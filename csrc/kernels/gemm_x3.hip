@@ -348,6 +348,8 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_x3g_kernel(const ConvParams
 
 // Split-K second pass: out = act(sum_s ws[s] + bias) (+ residual), the x3g epilogue per 4 channels of a pixel.
 // The partials are summed in split order, so the result does not depend on which split finished first.
+// Rounding: each partial is the fp32 accumulator of its own K range, stored unrounded; the splits - 1 adds below
+// round once each, before the bias (tests/fp32_bounds.py sk_adds puts them into the error model).
 __global__ __launch_bounds__(256) void x3g_sk_reduce_kernel(const ConvParams p) {
   const int HWo = p.Ho * p.Wo;
   const int M = live_batch(p.B, p.bdev) * HWo, Mcap = p.B * HWo;

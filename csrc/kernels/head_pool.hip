@@ -139,6 +139,9 @@ void head_pool(const HeadPoolParams& p, hipStream_t s) {
 // registers, one K slab ahead of use.
 // 8 waves x 32 channels = 256 output channels per workgroup (5 per crop for 1280): the staged, split pixel
 // block (the workgroup's fixed cost) is shared by twice the channels of a 4-wave workgroup.
+// Rounding: the six products of a K step accumulate in fp32, smallest first; bias + ReLU6 per pixel in fp32 (the
+// clamp precedes the mean); the pixel sum (in-lane, then xor-shuffles) and the scale by 1 / HW are fp32 too and
+// dominate the error of a pooled value of non-negative terms (tests/fp32_bounds.py, the pooled family).
 constexpr int kNSF = 256, kHeadF32Threads = 512;
 
 // The split pixel block is staged in two K halves of 160 channels (64 rows x 992 B = 62 KiB, a pitch of 2 (mod 4)

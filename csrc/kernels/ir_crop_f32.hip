@@ -24,6 +24,12 @@
 //     per workgroup; two barriers per chunk.
 //   y = acc + bp (+ x, stride 1)                                              fp32 NHWC
 //
+// Rounding: X, E and D are fp32 values re-split into three bf16 planes (exact to fp32 rounding); the expand and
+// project sums accumulate in fp32 on the matrix cores, the depthwise in fp32 FMAs.  Hidden slices add two more
+// points: with y_parts > 1 every slice stores its own fp32 project sum over its hidden chunks (P roundings in
+// place of one), and a consumer with x_parts > 1 adds the P partial tensors in order while loading, for the expand
+// operand and again for the residual (P - 1 fp32 adds each; tests/fp32_bounds.py carries both in its variance).
+//
 // Operand mapping of v_mfma_f32_16x16x32_bf16: lane l supplies A[row = l & 15][k = 8 (l >> 4) .. +7]
 // and B[k = 8 (l >> 4) .. +7][col = l & 15] and receives D[row = 4 (l >> 4) + r][col = l & 15].  Expand:
 // rows = hidden channels (A = We), columns = pixels (B = X).  Project: rows = output channels (A = Wp),

@@ -13,6 +13,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import fp32_bounds as fb
 from inference_arena_amd.ops import functional as AF
 
 pytestmark = pytest.mark.gpu
@@ -72,6 +73,9 @@ def test_conv_f32_matches_fp64(device, B, H, Cin, Cout, k, s, act, res, up):
     torch.cuda.synchronize()
     assert y.dtype == torch.float32
     _fp32_check(y.permute(0, 3, 1, 2), ref, scale)
+    case = fb.conv_case(B, H, Cin, Cout, k, s, act, res)
+    assert torch.equal(case.x, x32)
+    fb.check(case, y.permute(0, 3, 1, 2), "conv_f32")
     if up:
         up_ref = y.repeat_interleave(2, 1).repeat_interleave(2, 2)
         assert torch.equal(out2, up_ref)
@@ -118,6 +122,9 @@ def test_conv_x3g_matches_fp64(device, B, H, Cin, Cout, k, s, act, res, up):
     xd = _nhwc(x32).to(device)
     rd = _nhwc(r).to(device) if res else None
     packed = AF.pack_weights(w32, b32, device, "fp32")
+    case = fb.x3g_case(B, H, Cin, Cout, k, s, act, res)
+    assert torch.equal(case.x, x32)
+    bad = []
     for impl in X3G_IMPLS:
         out2 = torch.full((B, 2 * Ho, 2 * Ho, Cout), float("nan"), device=device) if up else None
         y = AF.conv2d_nhwc(xd, w32, b32, stride=s, act=act, res=rd, packed=packed, impl=impl, out2=out2)
@@ -126,6 +133,11 @@ def test_conv_x3g_matches_fp64(device, B, H, Cin, Cout, k, s, act, res, up):
         if up:
             want = y.permute(0, 3, 1, 2).repeat_interleave(2, 2).repeat_interleave(2, 3)
             assert torch.equal(out2.permute(0, 3, 1, 2), want), impl
+        try:  # split-K: the (splits - 1) workspace adds are part of sigma
+            fb.check(case, y.permute(0, 3, 1, 2), impl, adds=fb.sk_adds(impl, Cin, k))
+        except AssertionError as e:
+            bad.append((impl, str(e)))
+    assert not bad, bad
 
 
 def test_conv_x3g_channel_slices_and_live_batch(device):
@@ -138,6 +150,8 @@ def test_conv_x3g_channel_slices_and_live_batch(device):
     packed = AF.pack_weights(w, b, device, "fp32")
     ref = F.conv2d(buf[..., 32:64].permute(0, 3, 1, 2).double(), w.double(), b.double(), stride=2, padding=1)
     live = torch.tensor([3], dtype=torch.int32, device=device)
+    case = fb.slice_case(11, 12, 2)
+    assert torch.equal(case.buf, buf)
     for impl in X3G_IMPLS:
         out = torch.full((4, 6, 6, 128), 7.0, device=device)
         AF.conv2d_nhwc(buf.to(device), w, b, stride=2, act=None, x_coff=32, cin=32, out=out, out_coff=64,
@@ -146,6 +160,7 @@ def test_conv_x3g_channel_slices_and_live_batch(device):
         got = out[:3, :, :, 64:].permute(0, 3, 1, 2).double().cpu()
         assert (got - ref[:3]).abs().max().item() < 1e-5, impl
         assert torch.all(out[:, :, :, :64] == 7.0) and torch.all(out[3] == 7.0), impl
+        fb.check(case, got, impl, adds=fb.sk_adds(impl, 32, 3), live=3, rms=False)
 
 
 X3HG_IMPLS = [131 + v for v in range(14)]  # x3hg: 3x3 s1 halo tiles, 32x32x16 MFMA, pre-split weights
@@ -181,6 +196,8 @@ def test_conv_x3hg_matches_fp64(device, B, H, Cin, Cout, act, res, up, s):
     xd = _nhwc(x32).to(device)
     rd = _nhwc(r).to(device) if res else None
     packed = AF.pack_weights(w32, b32, device, "fp32")
+    case = fb.x3hg_case(B, H, Cin, Cout, act, res)
+    assert torch.equal(case.x, x32)
     bad = []
     for impl in X3HG_IMPLS:
         out2 = torch.full((B, 2 * Ho, 2 * Ho, Cout), float("nan"), device=device) if up else None
@@ -188,6 +205,7 @@ def test_conv_x3hg_matches_fp64(device, B, H, Cin, Cout, act, res, up, s):
         torch.cuda.synchronize()
         try:
             _fp32_check(y.permute(0, 3, 1, 2), ref, scale)
+            fb.check(case, y.permute(0, 3, 1, 2), impl)
         except AssertionError as e:
             bad.append((impl, str(e)))
             continue
@@ -217,7 +235,9 @@ def test_conv_x3hg_fused_pointwise_matches_fp64(device, B, H, Cin, C):
     scale = F.conv2d(1.2 * s1 + a.abs(), w2.double().abs(), b2.double().abs())
     xd = _nhwc(x).to(device)
     packed = AF.pack_weights(w, b, device, "fp32")
-    ran = 0
+    case = fb.pw_case(B, H, Cin, C)
+    assert torch.equal(case.x, x)
+    ran, bad = 0, []
     for impl in [0] + X3HG_PW_IMPLS:
         try:
             y = AF.conv2d_nhwc(xd, w, b, act="silu", packed=packed, impl=impl, pw=(w2, b2))
@@ -227,8 +247,13 @@ def test_conv_x3hg_fused_pointwise_matches_fp64(device, B, H, Cin, C):
         torch.cuda.synchronize()
         assert y.shape == (B, H, H, C)
         _fp32_check(y.permute(0, 3, 1, 2), ref, scale)
+        try:
+            fb.check(case, y.permute(0, 3, 1, 2), impl)
+        except AssertionError as e:
+            bad.append((impl, str(e)))
         ran += 1
     assert ran >= 3
+    assert not bad, bad
 
 
 # x3hg variant -> the x3hr variant with the same tile (TW, WM, WN, TM, TN)
@@ -272,6 +297,8 @@ def test_conv_x3hg_channel_slices_and_live_batch(device):
     packed = AF.pack_weights(w, b, device, "fp32")
     ref = F.conv2d(buf[..., 32:64].permute(0, 3, 1, 2).double(), w.double(), b.double(), padding=1)
     live = torch.tensor([3], dtype=torch.int32, device=device)
+    case = fb.slice_case(13, 11, 1)
+    assert torch.equal(case.buf, buf)
     for impl in X3HG_IMPLS:
         out = torch.full((4, 11, 11, 128), 7.0, device=device)
         AF.conv2d_nhwc(buf.to(device), w, b, stride=1, act=None, x_coff=32, cin=32, out=out, out_coff=64,
@@ -280,6 +307,7 @@ def test_conv_x3hg_channel_slices_and_live_batch(device):
         got = out[:3, :, :, 64:].permute(0, 3, 1, 2).double().cpu()
         assert (got - ref[:3]).abs().max().item() < 1e-5, impl
         assert torch.all(out[:, :, :, :64] == 7.0) and torch.all(out[3] == 7.0), impl
+        fb.check(case, got, impl, live=3, rms=False)
 
 
 @pytest.mark.parametrize(
@@ -314,7 +342,9 @@ def test_conv_x3_split_matches_fp64(device, B, H, Cin, Cout, k, s, act, res):
     xd = _nhwc(x32).to(device)
     rd = _nhwc(r).to(device) if res else None
     packed = AF.pack_weights(w32, b32, device, "fp32")
-    ran = 0
+    case = fb.conv_case(B, H, Cin, Cout, k, s, act, res)
+    assert torch.equal(case.x, x32)
+    ran, bad = 0, []
     for impl in X3_IMPLS:
         try:
             y = AF.conv2d_nhwc(xd, w32, b32, stride=s, act=act, res=rd, packed=packed, impl=impl)
@@ -323,8 +353,51 @@ def test_conv_x3_split_matches_fp64(device, B, H, Cin, Cout, k, s, act, res):
             continue
         torch.cuda.synchronize()
         _fp32_check(y.permute(0, 3, 1, 2), ref, scale)
+        try:
+            fb.check(case, y.permute(0, 3, 1, 2), impl)
+        except AssertionError as e:
+            bad.append((impl, str(e)))
         ran += 1
     assert ran >= 12
+    assert not bad, bad
+
+
+def _clamp_conv(device, case, k, impls, need):
+    """A clamp-reaching ReLU6 conv case through ``impls`` (0: the dispatch policy): the fp32 bound and both tiers."""
+    fb.assert_clamped(case)
+    st = case.stages[0]
+    x64, w64, b64 = case.x.double(), st["w"].double(), st["b"].double()
+    ref = _act64(F.conv2d(x64, w64, b64, padding=k // 2), "relu6")
+    scale = F.conv2d(x64.abs(), w64.abs(), b64.abs(), padding=k // 2)
+    xd = _nhwc(case.x).to(device)
+    packed = AF.pack_weights(st["w"], st["b"], device, "fp32")
+    ran, bad = 0, []
+    for impl in impls:
+        try:
+            y = AF.conv2d_nhwc(xd, st["w"], st["b"], act="relu6", packed=packed, impl=impl)
+        except RuntimeError as e:
+            assert impl != 0 and "eligible" in str(e), (impl, e)
+            continue
+        torch.cuda.synchronize()
+        try:
+            _fp32_check(y.permute(0, 3, 1, 2), ref, scale)
+            fb.check(case, y.permute(0, 3, 1, 2), impl, adds=fb.sk_adds(impl, case.x.shape[1], k))
+        except AssertionError as e:
+            bad.append((impl, str(e)))
+        ran += 1
+    assert ran >= need, ran
+    assert not bad, bad
+
+
+def test_conv_relu6_reaches_the_clamp(device):
+    """MobileNet expand geometry (160 -> 960, 7 x 7) with the input x 3: about 2 % of the pre-activations above 6.
+    conv_f32 (the dispatch policy), every x3g variant incl. split-K and the x3 split tiles."""
+    _clamp_conv(device, fb.conv_clamp_case("conv", *fb.CLAMP_CONV), 1, [0] + X3_IMPLS + X3G_IMPLS[20:], 1 + 12 + 9)
+
+
+def test_conv_x3hg_relu6_reaches_the_clamp(device):
+    """The Cin 20 halo case with the input x 3, every x3hg / x3hr variant."""
+    _clamp_conv(device, fb.conv_clamp_case("x3hg", *fb.CLAMP_X3HG), 3, X3HG_IMPLS, len(X3HG_IMPLS))
 
 
 @pytest.mark.parametrize("B,live", [(17, None), (32, 16), (32, 17)])
@@ -345,6 +418,9 @@ def test_fc_f32_crop_tiles(device, B, live):
     n = B if live is None else live
     _fp32_check(out.permute(0, 3, 1, 2)[:n], ref[:n], scale[:n])
     assert torch.all(out[n:] == -7.0), "rows past the live count must not be written"
+    case = fb.fc_case(B, live)
+    assert torch.equal(case.x, x)
+    fb.check(case, out.permute(0, 3, 1, 2), "fc_splitk", live=n)
 
 
 def test_conv_f32_channel_slices(device):
@@ -373,6 +449,22 @@ def test_dwconv_f32(device, stride, H):
     torch.cuda.synchronize()
     ref = F.relu6(F.conv2d(x.double(), w.double(), b.double(), stride=stride, padding=1, groups=C))
     np.testing.assert_allclose(y.permute(0, 3, 1, 2).double().cpu().numpy(), ref.numpy(), rtol=1e-6, atol=1e-6)
+    case = fb.dw_case(stride, H)
+    assert torch.equal(case.x, x)
+    fb.check(case, y.permute(0, 3, 1, 2), "dwconv3x3")
+
+
+@pytest.mark.parametrize("stride,H", fb.CLAMP_DW)
+def test_dwconv_f32_reaches_the_relu6_clamp(device, stride, H):
+    """Weights x 3: the upper clamp is reached (a ReLU in its place would differ), same tolerance and tiers."""
+    case = fb.dw_case(stride, H, gain=fb.DW_CLAMP_GAIN)
+    fb.assert_clamped(case)
+    st = case.stages[0]
+    y = AF.dwconv3x3_nhwc(_nhwc(case.x).to(device), st["w"], st["b"], stride=stride, act="relu6")
+    torch.cuda.synchronize()
+    ref = case.refs()[0]
+    np.testing.assert_allclose(y.permute(0, 3, 1, 2).double().cpu().numpy(), ref.numpy(), rtol=1e-6, atol=1e-6)
+    fb.check(case, y.permute(0, 3, 1, 2), "dwconv3x3")
 
 
 def test_sppf_f32_exact(device):
@@ -658,6 +750,59 @@ def test_ir_block_f32_matches_fp64(device, inp, hid, oup, stride, H, res, x3t, m
     got = y.permute(0, 3, 1, 2).double().cpu()
     err = (got - ref).abs().max().item()
     assert err < 2e-5 * (1.0 + ref.abs().max().item()), err
+    case = fb.ir_case(inp, hid, oup, stride, H, res)
+    assert torch.equal(case.x, x)
+    fb.check(case, got, f"x3t={x3t}")
+
+
+def _s2k16_default():
+    import os
+
+    try:  # the library's own default: the environment variable read as an integer, on when unset
+        return int(os.environ.get("ARENA_IR_S2K16", "1")) != 0
+    except ValueError:
+        return False
+
+
+# (inp, hid, oup, stride, H, res) of fb.CLAMP_IR x the kernels that take the shape
+CLAMP_IR_RUNS = [
+    ((32, 32, 16, 1, 20, False), "x3t=1"), ((32, 32, 16, 1, 20, False), "x3t=0"),      # t = 1: the depthwise clamp only
+    ((16, 96, 24, 2, 17, False), "s2k16=1"), ((16, 96, 24, 2, 17, False), "s2k16=0"),  # ir_s2k16_x3 / ir_f32
+    ((24, 144, 24, 1, 19, True), "x3t=1"), ((24, 144, 24, 1, 19, True), "x3t=0"),      # partial tiles, a partial strip
+    ((32, 192, 64, 2, 28, False), "x3t=1"),
+    ((64, 384, 96, 1, 14, False), "bands=2"), ((64, 384, 96, 1, 14, False), "bands=4"),
+    ((96, 576, 160, 2, 14, False), "bands=2"),
+    ((160, 960, 160, 1, 7, True), "bands=2"),
+]
+
+
+@pytest.mark.parametrize("shape,how", CLAMP_IR_RUNS, ids=lambda v: v if isinstance(v, str) else "-".join(map(str, map(int, v))))
+def test_ir_block_f32_reaches_the_relu6_clamp(device, shape, how, monkeypatch, request):
+    """Expand and depthwise weights x 2.5: both ReLU6 stages reach the upper clamp (checked on the fp64 reference
+    first), so a kernel with ReLU in place of ReLU6 fails.  Same per-element formula, same tiers."""
+    from inference_arena_amd.ops import native
+
+    assert shape in fb.CLAMP_IR
+    inp, hid, oup, stride, H, res = shape
+    case = fb.ir_case(*shape, gain=fb.CLAMP_GAIN, B=2)
+    fb.assert_clamped(case)
+    key, val = how.split("=")
+    if key == "bands":
+        monkeypatch.setenv("ARENA_IRC_F32", "1")
+        native().set_irx_parts(int(val))
+        request.addfinalizer(lambda: native().set_irx_parts(-1))
+    elif key == "s2k16":
+        native().set_ir_s2k16(val == "1")
+        request.addfinalizer(lambda: native().set_ir_s2k16(_s2k16_default()))
+    else:
+        monkeypatch.setenv("ARENA_IR_X3T", val)
+    expand, dw, project = case.blocks[0][:3]
+    y = AF.ir_block_nhwc(_nhwc(case.x).to(device), expand, dw, project, stride=stride, res=res)
+    ref = _ir_ref64(case.x, expand, dw, project, stride, res)
+    got = y.permute(0, 3, 1, 2).double().cpu()
+    err = (got - ref).abs().max().item()
+    assert err < 2e-5 * (1.0 + ref.abs().max().item()), err
+    fb.check(case, got, how)
 
 
 @pytest.mark.parametrize("parts,crops", [(2, 5), (3, 5), (6, 5), (6, 40)])
@@ -689,6 +834,29 @@ def test_ir_block_f32_hidden_slices_chain(device, parts, crops, bands, request):
     assert err < 2e-5 * (1.0 + ref.abs().max().item()), err
     summed = mid.reshape(crops, 14, 14, parts, 96)[..., :eff, :].double().sum(3).permute(0, 3, 1, 2).cpu()
     assert (summed - r0).abs().max().item() < 2e-5 * (1.0 + r0.abs().max().item())
+    case = fb.ir_chain_case(parts, crops, bands)
+    assert torch.equal(case.x, x)
+    fb.check(case, got, "chain")
+
+
+def test_ir_block_f32_hidden_slices_chain_reaches_the_relu6_clamp(device, request):
+    """The hidden-slice chain with parts = 3 and the expand / depthwise weights x 2.5: the clamp inside sliced blocks."""
+    from inference_arena_amd.ops import native
+
+    parts = 3
+    native().set_irx_parts(2)
+    native().set_irx_slices_big(3)
+    request.addfinalizer(lambda: (native().set_irx_parts(-1), native().set_irx_slices_big(-1)))
+    case = fb.ir_chain_case(parts, 5, 2, gain=fb.CLAMP_GAIN)
+    fb.assert_clamped(case)
+    (ea, da, pa), (eb, db, pb) = case.blocks[0][:3], case.blocks[1][:3]
+    mid = AF.ir_block_nhwc(_nhwc(case.x).to(device), ea, da, pa, stride=1, res=False, y_parts=parts)
+    y = AF.ir_block_nhwc(mid, eb, db, pb, stride=1, res=True, x_parts=parts)
+    ref = case.refs()[0]
+    got = y.permute(0, 3, 1, 2).double().cpu()
+    err = (got - ref).abs().max().item()
+    assert err < 2e-5 * (1.0 + ref.abs().max().item()), err
+    fb.check(case, got, "chain")
 
 
 @pytest.mark.parametrize("parts", [1, 3, 5])
@@ -714,6 +882,9 @@ def test_ir_block_f32_hidden_slices_tail(device, parts, monkeypatch):
     got = y.permute(0, 3, 1, 2).double().cpu()
     err = (got - ref).abs().max().item()
     assert err < 2e-5 * (1.0 + ref.abs().max().item()), err
+    case = fb.ir_tail_case(parts)
+    assert torch.equal(case.x, x)
+    fb.check(case, got, "tail")
 
 
 @pytest.mark.parametrize("B,H,W", [(2, 24, 48), (1, 8, 16), (3, 16, 32)])
@@ -736,6 +907,9 @@ def test_c3_x3_matches_fp64(device, B, H, W):
     got = y.permute(0, 3, 1, 2).double().cpu()
     err = (got - ref).abs().max().item()
     assert err < 2e-5 * (1.0 + ref.abs().max().item()), err
+    case = fb.c3_case(B, H, W)
+    assert torch.equal(case.x, x)
+    fb.check(case, got, "c3_x3")
 
 
 def test_fp32_fused_c3_program_matches_unfused(dense_models, device, monkeypatch):
@@ -791,5 +965,22 @@ def test_head_pool_f32_matches_fp64(device, B, HW):
     ref = F.conv2d(x.double(), w.double(), b.double()).clamp(0, 6).mean(dim=(2, 3))
     scale = F.conv2d(x.double().abs(), w.double().abs(), b.double().abs()).mean(dim=(2, 3))
     _fp32_check(y.double().cpu(), ref, scale, rel=4e-6)
+    case = fb.head_pool_case(B, HW)
+    assert torch.equal(case.x, x)
+    fb.check(case, y, "head_pool")
+
+
+@pytest.mark.parametrize("B,HW", fb.CLAMP_HEAD_POOL)
+def test_head_pool_f32_reaches_the_relu6_clamp(device, B, HW):
+    """Head weights x 2.5: the clamp precedes the mean, so a ReLU in its place would shift the pooled value."""
+    case = fb.head_pool_case(B, HW, gain=fb.CLAMP_GAIN)
+    fb.assert_clamped(case)
+    st = case.stages[0]
+    y = AF.head_pool_nhwc(_nhwc(case.x).to(device), st["w"], st["b"], "relu6")
+    x64, w64, b64 = case.x.double(), st["w"].double(), st["b"].double()
+    ref = F.conv2d(x64, w64, b64).clamp(0, 6).mean(dim=(2, 3))
+    scale = F.conv2d(x64.abs(), w64.abs(), b64.abs()).mean(dim=(2, 3))
+    _fp32_check(y.double().cpu(), ref, scale, rel=4e-6)
+    fb.check(case, y, "head_pool")
 
 

@@ -12,6 +12,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import fp32_bounds as fb
 from inference_arena_amd.ops import functional as AF
 
 pytestmark = pytest.mark.gpu
@@ -67,6 +68,9 @@ def test_ir_tile_strips_match_fp64(device, inp, hid, oup, stride, H, res, monkey
     err = (got - ref).abs().max().item()
     print(f"max abs err {err:.3g}, bound {2e-5 * (1.0 + ref.abs().max().item()):.3g}")
     assert err < 2e-5 * (1.0 + ref.abs().max().item()), err
+    case = fb.strips_case(inp, hid, oup, stride, H, res)
+    assert torch.equal(case.x, x)
+    fb.check(case, got, "ir_tile_x3")
 
 
 def test_ir_tile_strips_live_batch(device, monkeypatch):
@@ -92,6 +96,9 @@ def test_ir_tile_strips_live_batch(device, monkeypatch):
     got = y.permute(0, 3, 1, 2).double().cpu()
     err = (got[:2] - ref[:2]).abs().max().item()
     assert err < 2e-5 * (1.0 + ref.abs().max().item()), err
+    case = fb.strips_case(inp, hid, oup, stride, H, True)
+    assert torch.equal(case.x, x)
+    fb.check(case, got, "ir_tile_x3 live", live=2)
     assert torch.equal(y[2].cpu(), torch.full_like(y[2].cpu(), sentinel))
 
 

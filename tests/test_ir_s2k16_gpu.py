@@ -14,6 +14,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import fp32_bounds as fb
 from inference_arena_amd.ops import functional as AF
 
 pytestmark = pytest.mark.gpu
@@ -52,7 +53,9 @@ def _case(H, W, B):
         expand = (torch.randn(HID, INP, 1, 1, generator=g) / INP ** 0.5, torch.randn(HID, generator=g) * 0.1)
         dw = (torch.randn(HID, 1, 3, 3, generator=g) / 3, torch.randn(HID, generator=g) * 0.1)
         project = (torch.randn(OUP, HID, 1, 1, generator=g) / HID ** 0.5, torch.randn(OUP, generator=g) * 0.1)
-        _cases[key] = (x, expand, dw, project, _ir_ref64(x, expand, dw, project, STRIDE, False))
+        zc = fb.s2k16_case(H, W, B)  # the same draws: its fp64 variance model for the two tiers of fp32_bounds.py
+        assert torch.equal(zc.x, x)
+        _cases[key] = (x, expand, dw, project, _ir_ref64(x, expand, dw, project, STRIDE, False), zc)
     return _cases[key]
 
 
@@ -73,7 +76,7 @@ def s2k16(request):
 
 
 def _run(device, case, **kw):
-    x, expand, dw, project, _ = case
+    x, expand, dw, project = case[:4]
     y = AF.ir_block_nhwc(_nhwc(x).to(device), expand, dw, project, stride=STRIDE, res=False, **kw)
     return y
 
@@ -98,6 +101,7 @@ def test_block2_matches_fp64(device, s2k16, H, W, B, on):
     err = (got - ref).abs().max().item()
     print(f"s2k16={on} {H}x{W}x{B}: max abs err {err:.3g}, bound {_bound(ref):.3g}")
     assert err < _bound(ref), err
+    fb.check(case[5], got, f"s2k16={on}")
 
 
 @pytest.mark.parametrize("on", [1, 0])
@@ -112,6 +116,7 @@ def test_block2_live_batch(device, s2k16, on):
     got = _nchw64(y)
     err = (got[:3] - ref[:3]).abs().max().item()
     assert err < _bound(ref[:3]), err
+    fb.check(case[5], got, f"s2k16={on} live", live=3)
     assert torch.equal(y[3:].cpu(), torch.full((2, 10, 10, OUP), SENTINEL))
 
 
@@ -126,6 +131,7 @@ def test_block2_channel_guard(device, s2k16, on):
     assert torch.equal(y[..., OUP:], torch.full((3, 19, 19, 32 - OUP), SENTINEL))
     err = (_nchw64(y[..., :OUP]) - ref).abs().max().item()
     assert err < _bound(ref), err
+    fb.check(case[5], _nchw64(y[..., :OUP]), f"s2k16={on} guard")
 
 
 def test_block2_new_against_old(device, s2k16):

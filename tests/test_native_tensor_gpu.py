@@ -17,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 import detect_cases as dc
+import fp32_bounds as fb
 from inference_arena_amd.models.common import fold
 from inference_arena_amd.ops import functional as AF
 from inference_arena_amd.ops import native
@@ -87,7 +88,8 @@ def refs(front):
         # second conv: the stem's error carried through |w1| and the closing SiLU, plus the conv's own bound
         bound = SILU_LIP * F.conv2d(e_a, front["w1"].abs(), None, stride=2, padding=1) + \
             FP32_REL * F.conv2d(a.abs(), front["w1"].abs(), front["b1"].abs(), stride=2, padding=1) + 1e-30
-        out[name] = (x, ref, bound)
+        zc = fb.front_case(name, x, front["w0"].float(), front["b0"].float(), front["w1"].float(), front["b1"].float())
+        out[name] = (x, ref, bound, zc)
     return out
 
 
@@ -97,7 +99,7 @@ def test_tensor_front_end_matches_fp64(device, front, refs, monkeypatch, name, t
     """Every element of both live images within the propagated fp64 bound, no NaN, the dead image untouched."""
     monkeypatch.setenv("ARENA_STEM_X3_TH", th)
     monkeypatch.setenv("ARENA_STEM_X3_NW", nw)
-    x, ref, bound = refs[name]
+    x, ref, bound, zc = refs[name]
     meta, pool = dc.tensor_pool(x)
     meta_t = torch.frombuffer(bytearray(meta), dtype=torch.uint8).to(device)
     pool_t = torch.from_numpy(pool.copy()).to(device)
@@ -116,6 +118,7 @@ def test_tensor_front_end_matches_fp64(device, front, refs, monkeypatch, name, t
     worst = (err / bound[:LIVE]).max().item()
     print(f"{name} <{th},{nw}>: max error {err.max().item():.3e}, {worst:.3f} of the bound")
     assert worst <= 1.0, (name, th, nw, err.max().item(), worst)
+    fb.check(zc, g, f"<{th},{nw}>", live=LIVE)
 
 
 def test_fp32_yolo_raw_fused_front_matches_unfused(models, device, monkeypatch):

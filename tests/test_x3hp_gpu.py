@@ -12,6 +12,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import fp32_bounds as fb
 from inference_arena_amd.ops import functional as AF
 
 pytestmark = pytest.mark.gpu
@@ -81,11 +82,14 @@ def test_conv_x3hp_matches_fp64_and_old_halo_bits(device, B, H, Cin, Cout, act, 
             assert (9 * Cin) % 16 != 0 or impl != 101, "impl 101 must take this shape"
     assert (101 in old) == ((9 * Cin) % 16 == 0)
 
+    case = fb.x3hg_case(B, H, Cin, Cout, act, res)  # the inputs of test_fp32_gpu.py::test_conv_x3hg_matches_fp64
+    assert torch.equal(case.x, x32)
     bad = []
     for impl in X3HP_IMPLS:
         y, out2 = run(impl)
         try:
             _fp32_check(y.permute(0, 3, 1, 2), ref, scale)
+            fb.check(case, y.permute(0, 3, 1, 2), impl)
         except AssertionError as e:
             bad.append((impl, str(e)))
             continue
@@ -110,6 +114,8 @@ def test_conv_x3hp_channel_slices_and_live_batch(device):
     packed = AF.pack_weights(w, b, device, "fp32")
     ref = F.conv2d(buf[..., 32:64].permute(0, 3, 1, 2).double(), w.double(), b.double(), padding=1)
     live = torch.tensor([3], dtype=torch.int32, device=device)
+    case = fb.slice_case(13, 11, 1)
+    assert torch.equal(case.buf, buf)
     want = None
     for impl in [101] + X3HP_IMPLS:
         out = torch.full((4, 11, 11, 128), 7.0, device=device)
@@ -119,6 +125,30 @@ def test_conv_x3hp_channel_slices_and_live_batch(device):
         got = out[:3, :, :, 64:].permute(0, 3, 1, 2).double().cpu()
         assert (got - ref[:3]).abs().max().item() < 1e-5, impl
         assert torch.all(out[:, :, :, :64] == 7.0) and torch.all(out[3] == 7.0), impl
+        fb.check(case, got, impl, live=3, rms=False)
         if want is None:
             want = out
         assert torch.equal(out, want), impl
+
+
+def test_conv_x3hp_relu6_reaches_the_clamp(device):
+    """The Cin 20 case with its input x 3 (about 1.5 % of the pre-activations above 6): a ReLU in place of ReLU6
+    would differ.  Every x3hp variant under the fp32 bound and both tiers of fp32_bounds.py."""
+    case = fb.conv_clamp_case("x3hg", *fb.CLAMP_X3HG)
+    fb.assert_clamped(case)
+    st = case.stages[0]
+    x64, w64, b64 = case.x.double(), st["w"].double(), st["b"].double()
+    ref = _act64(F.conv2d(x64, w64, b64, padding=1), "relu6")
+    scale = F.conv2d(x64.abs(), w64.abs(), b64.abs(), padding=1)
+    xd = _nhwc(case.x).to(device)
+    packed = AF.pack_weights(st["w"], st["b"], device, "fp32")
+    bad = []
+    for impl in X3HP_IMPLS:
+        y = AF.conv2d_nhwc(xd, st["w"], st["b"], act="relu6", packed=packed, impl=impl)
+        torch.cuda.synchronize()
+        try:
+            _fp32_check(y.permute(0, 3, 1, 2), ref, scale)
+            fb.check(case, y.permute(0, 3, 1, 2), impl)
+        except AssertionError as e:
+            bad.append((impl, str(e)))
+    assert not bad, bad
