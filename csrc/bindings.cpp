@@ -327,6 +327,47 @@ void py_stem_s2_f32(const py::dict& d) {
   stem_s2_f32(p, stream_of(d));
 }
 
+// bf16 front ends on their own (csrc/kernels/stem_fused.hip): src 0 letterbox -> detector stem [-> 3x3 s2 conv with
+// "w2"], src 1 crop gather -> classifier stem [-> MobileNetV2 block 1 with "ir_wd"].
+void py_stem_fused(const py::dict& d) {
+  StemFusedParams p{};
+  p.src = req<int>(d, "src");
+  p.pool = ptr<const uint8_t*>(d, "pool");
+  p.meta = ptr<const ImageMeta*>(d, "meta");
+  p.ctrl = ptr<const Ctrl*>(d, "ctrl");
+  p.crops = ptr<const CropRef*>(d, "crops");
+  p.cap = req<int>(d, "cap");
+  p.S = req<int>(d, "S");
+  const auto mean = get<std::vector<float>>(d, "mean", {0.f, 0.f, 0.f});
+  const auto inv_std = get<std::vector<float>>(d, "inv_std", {1.f, 1.f, 1.f});
+  for (int c = 0; c < 3; ++c) {
+    p.mean[c] = mean.at(c);
+    p.inv_std[c] = inv_std.at(c);
+  }
+  p.KS = req<int>(d, "KS");
+  p.w = ptr<const void*>(d, "w");
+  p.Kpad = req<int>(d, "Kpad");
+  p.bias = ptr<const float*>(d, "bias");
+  p.Cout = req<int>(d, "Cout");
+  p.y = ptr<void*>(d, "y");
+  p.ys = get<int>(d, "ys", 0);
+  p.act = get<int>(d, "act", 0);
+  p.w2 = ptr<const void*>(d, "w2");
+  p.Kpad2 = get<int>(d, "Kpad2", 0);
+  p.bias2 = ptr<const float*>(d, "bias2");
+  p.Cout2 = get<int>(d, "Cout2", 0);
+  p.act2 = get<int>(d, "act2", 0);
+  p.y2 = ptr<void*>(d, "y2");
+  p.y2s = get<int>(d, "y2s", 0);
+  p.ir_wd = ptr<const void*>(d, "ir_wd");
+  p.ir_bd = ptr<const float*>(d, "ir_bd");
+  p.ir_wp = ptr<const void*>(d, "ir_wp");
+  p.ir_bp = ptr<const float*>(d, "ir_bp");
+  p.ir_y = ptr<void*>(d, "ir_y");
+  p.ir_ys = get<int>(d, "ir_ys", 0);
+  stem_fused(p, stream_of(d));
+}
+
 // {"name", "input", "in_dims", "output", "out_dims", "max_batch_size", "platform", "versions"} -> the contract
 KServeTensorModel tensor_model_of(const py::dict& d) {
   KServeTensorModel m;
@@ -752,6 +793,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("yolo_raw", &py_yolo_raw);
   m.def("tensor_in_s2d", &py_tensor_in);
   m.def("stem_s2_f32", &py_stem_s2_f32);
+  m.def("stem_fused", &py_stem_fused);
   m.def("nms", &py_nms);
   m.def("crop_plan", &py_crop_plan);
   m.def("crop_gather_s2d", &py_crop_gather);

@@ -1,7 +1,8 @@
 // Letterbox sampling shared by the standalone letterbox kernel (preprocess.hip) and the fp32 stem conv that
 // reads the uint8 image directly (conv_f32.hip, impl kF32X3H16 with a letterbox source): both produce the
 // space-to-depth(2) pixel through letterbox_s2d_px, so the fused and unfused programs see bitwise the same
-// input values.
+// input values.  The fused bf16 front ends (stem_fused.hip) take lin_tap, div255 and crop_norm from here and keep
+// a two-column form of bilinear_rgb under the same `fp contract(off)`.
 //
 // Reference semantics: src/shared/processing/transforms.py:118-180 (scale = min(T/h, T/w), int-truncated
 // new size, floor-centred pad, gray 114, cv2 INTER_LINEAR) and src/shared/processing/yolo_preprocess.py:154-167
@@ -57,6 +58,13 @@ template <typename T>
 __device__ __forceinline__ float div255(float v) {
   if constexpr (sizeof(T) == 4) return v / 255.0f;
   else return v * (1.0f / 255.0f);
+}
+
+// ImageNet normalisation of a uint8 level, the value crop_gather_s2d stores: one expression for the standalone
+// kernel (preprocess.hip) and the fused front ends (stem_fused.hip), which must agree bit for bit.
+template <typename T>
+__device__ __forceinline__ float crop_norm(float v, float mean, float inv_std) {
+  return (div255<T>(v) - mean) * inv_std;
 }
 
 // The 12 live channels of letterboxed space-to-depth pixel (Y, X) of image m as uint8 values (exact small

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void crop_gather_s2d_kernel(const CropGatherPa
     float rgb[3] = {0.f, 0.f, 0.f};
     if (!empty) bilinear_rgb(img, m.w, lin_tap(oy, sy, ch), lin_tap(ox, sx, cw), rgb);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) out[pq * 3 + c] = (div255<T>(rgb[c]) - p.mean[c]) * p.inv_std[c];
+    for (int c = 0; c < 3; ++c) out[pq * 3 + c] = crop_norm<T>(rgb[c], p.mean[c], p.inv_std[c]);
   }
   out[12] = out[13] = out[14] = out[15] = 0.f;
   store16((T*)p.out + (size_t)tid * 16, out);

@@ -22,32 +22,27 @@
 // Blocks are mapped so that all tiles of an image run on one XCD (the
 // source image's rows are re-read by neighbouring tiles from that L2).
 //
-// Numerics are identical to letterbox_s2d / crop_gather_s2d followed by the
-// stem conv: the same float ops produce the same bf16 s2d values.
+// Numerics, as tests/test_stem_fused_gpu.py pins them: every bf16 value of the LDS s2d tile is bit for bit the
+// value letterbox_s2d / crop_gather_s2d (preprocess.hip) store for that pixel, zero outside the S/2 x S/2 map.
+// The tap coordinates (lin_tap), the bilinear lerps and the ImageNet normalisation (crop_norm) are the
+// separately rounded operations of letterbox.h; bilinear_pair below is bilinear_rgb on two columns at once under
+// the same `fp contract(off)`: a fused multiply-add moves samples that sit at x.5 to the other side of the uint8
+// rounding.  `ident` (both scales exactly 1.f, which for sizes below 2^24 means new_h == h && new_w == w, the
+// `unit` test of letterbox.h) copies source bytes; at unit scale every lerp weight is 0, so this is the same value.
+// bf16 rounds at: the s2d tile (once, from the fp32 normalised sample), the stem output of stem2_kernel /
+// stem_ir_kernel and the depthwise output of stem_ir_kernel (LDS stores of the fp32 accumulator after bias and
+// activation; zero outside the map), and every global store.  The convs accumulate bf16 x bf16 in fp32.
+//
+// The image pool needs slack: the staged path loads whole aligned dwords, up to 3 bytes in front of a source row
+// (inside the pool: images start 256-byte aligned) and up to 7 bytes behind its end, so at least 8 readable bytes
+// must follow the last image (ops.functional.image_pool; the executor's pool is a fixed-size arena).
 #include "common.h"
 #include "launch.h"
+#include "letterbox.h"
 
 namespace arena {
 
 namespace {
-
-struct LinTap2 {
-  int i0, i1;
-  float f;
-};
-
-__device__ __forceinline__ LinTap2 tap_of(int d, float scale, int n) {
-  float fx = ((float)d + 0.5f) * scale - 0.5f;
-  int s0 = (int)floorf(fx);
-  float f = fx - (float)s0;
-  if (s0 < 0) { s0 = 0; f = 0.f; }
-  if (s0 >= n - 1) { s0 = n - 1; f = 0.f; }
-  LinTap2 t;
-  t.i0 = s0;
-  t.i1 = s0 + 1 < n ? s0 + 1 : n - 1;
-  t.f = f;
-  return t;
-}
 
 struct RowTap {
   int o0, o1;  // byte offsets of the two taps (o0 < 0: outside the sampled area)
@@ -57,12 +52,14 @@ struct RowTap {
 typedef float float2v __attribute__((ext_vector_type(2)));
 
 // Both sub-pixel columns of one sub-pixel row (the pair shares the row taps),
-// in packed fp32 (v_pk_fma_f32 / v_pk_add_f32).  `ident` (scale exactly 1,
+// in packed fp32 (v_pk_mul_f32 / v_pk_add_f32: the rounded operations of
+// bilinear_rgb, never a fused multiply-add).  `ident` (scale exactly 1,
 // so every lerp weight is 0): the sample is the source byte itself, as
 // cv2.resize copies at equal sizes.  Columns outside the sampled area keep
 // `pad`.
 __device__ __forceinline__ void bilinear_pair(const uint8_t* base, const RowTap& ry, const RowTap& c0,
                                               const RowTap& c1, bool ident, float pad, float2v* rgb) {
+#pragma clang fp contract(off)  // as bilinear_rgb (letterbox.h): separately rounded multiply and add
   const bool v0 = c0.o0 >= 0, v1 = c1.o0 >= 0;
   if (!v0 && !v1) return;
   const int a0 = v0 ? c0.o0 : c1.o0, a1 = v1 ? c1.o0 : c0.o0;  // an invalid column reads its valid neighbour
@@ -164,9 +161,9 @@ __device__ __forceinline__ void build_s2d_tile(const StemFusedParams& p, const S
   int r_lo = 0, c_lo = 0, pitch = 0;
   const size_t row_bytes = (size_t)g.stride_px * 3;
   if (!g.empty && sy_lo <= sy_hi && sx_lo <= sx_hi) {
-    r_lo = tap_of(sy_lo, g.sy, g.rh).i0;
-    c_lo = tap_of(sx_lo, g.sx, g.rw).i0;
-    const int r_hi = tap_of(sy_hi, g.sy, g.rh).i1, c_hi = tap_of(sx_hi, g.sx, g.rw).i1;
+    r_lo = lin_tap(sy_lo, g.sy, g.rh).i0;
+    c_lo = lin_tap(sx_lo, g.sx, g.rw).i0;
+    const int r_hi = lin_tap(sy_hi, g.sy, g.rh).i1, c_hi = lin_tap(sx_hi, g.sx, g.rw).i1;
     const int nrows = r_hi - r_lo + 1, rbytes = (c_hi - c_lo + 1) * 3;
     const int ndw = (rbytes + 3 + 3) >> 2;  // up to 3 bytes of alignment shift in front
     pitch = ndw * 4;
@@ -193,7 +190,7 @@ __device__ __forceinline__ void build_s2d_tile(const StemFusedParams& p, const S
     const int d = 2 * sY0 + (int)threadIdx.x - g.pad_h;
     RowTap e{-1, -1, 0.f};
     if (!g.empty && d >= 0 && d < (SRC == 0 ? g.h : p.S)) {
-      const LinTap2 t = tap_of(d, g.sy, g.rh);
+      const LinTap t = lin_tap(d, g.sy, g.rh);
       if (staged) {
         const int r0 = t.i0 - r_lo, r1 = t.i1 - r_lo;
         e.o0 = r0 * pitch + (int)((base_addr + (size_t)r0 * row_bytes) & 3);
@@ -210,7 +207,7 @@ __device__ __forceinline__ void build_s2d_tile(const StemFusedParams& p, const S
     const int d = 2 * sX0 + k - g.pad_w;
     RowTap e{-1, -1, 0.f};
     if (!g.empty && d >= 0 && d < (SRC == 0 ? g.w : p.S)) {
-      const LinTap2 t = tap_of(d, g.sx, g.rw);
+      const LinTap t = lin_tap(d, g.sx, g.rw);
       const int c0 = staged ? c_lo : 0;
       e.o0 = (t.i0 - c0) * 3;
       e.o1 = (t.i1 - c0) * 3;
@@ -245,8 +242,8 @@ __device__ __forceinline__ void build_s2d_tile(const StemFusedParams& p, const S
 #pragma unroll
           for (int b = 0; b < 2; ++b) {
             const float v = b ? rgb[c].y : rgb[c].x;
-            if constexpr (SRC == 0) out[(a * 2 + b) * 3 + c] = v * (1.0f / 255.0f);
-            else out[(a * 2 + b) * 3 + c] = (v * (1.0f / 255.0f) - p.mean[c]) * p.inv_std[c];
+            if constexpr (SRC == 0) out[(a * 2 + b) * 3 + c] = div255<bf16>(v);
+            else out[(a * 2 + b) * 3 + c] = crop_norm<bf16>(v, p.mean[c], p.inv_std[c]);
           }
         }
       }
@@ -594,6 +591,8 @@ void stem_fused(const StemFusedParams& p, hipStream_t s) {
   if (p.S % 2 != 0 || p.S <= 0) throw std::runtime_error("stem_fused: S must be positive and even");
   if (p.ctrl == nullptr) throw std::runtime_error("stem_fused: needs the control block (live counts)");
   if (p.ys % 4 != 0) throw std::runtime_error("stem_fused: output pixel stride must be a multiple of 4");
+  if (p.pool == nullptr || p.meta == nullptr || p.w == nullptr || p.bias == nullptr)
+    throw std::runtime_error("stem_fused: needs the image pool, the image records and the stem weights");
   if (p.cap <= 0) return;
   if (p.src == 0) {  // YOLOv5nu: letterbox -> 6x6/s2 stem as 3x3/s1 over s2d, 16 channels, SiLU
     if (p.KS != 3 || p.Cout != 16 || p.Kpad != 160)
@@ -606,6 +605,7 @@ void stem_fused(const StemFusedParams& p, hipStream_t s) {
       hipLaunchKernelGGL((stem2_kernel<8, 16>), dim3((unsigned)blocks), dim3(256), 0, s, p);
       return;
     }
+    if (p.y == nullptr) throw std::runtime_error("stem_fused: needs an output");
     stem_launch<0, 3, 1, 8, 32>(p, s);
   } else if (p.src == 1) {  // MobileNetV2: crop gather -> 3x3/s2 stem as 2x2/s1 over s2d, 32 channels, ReLU6
     if (p.KS != 2 || p.Cout != 32 || p.Kpad != 64 || p.crops == nullptr)
@@ -619,6 +619,7 @@ void stem_fused(const StemFusedParams& p, hipStream_t s) {
       hipLaunchKernelGGL((stem_ir_kernel<16>), dim3((unsigned)blocks), dim3(256), 0, s, p);
       return;
     }
+    if (p.y == nullptr) throw std::runtime_error("stem_fused: needs an output");
     stem_launch<1, 2, 2, 16, 16>(p, s);
   } else {
     throw std::runtime_error("stem_fused: unknown source");

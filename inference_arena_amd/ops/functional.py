@@ -325,6 +325,101 @@ def letterbox_s2d(images: list[np.ndarray], T: int, device, dtype=torch.bfloat16
     return out
 
 
+POOL_SLACK = 8  # bytes the staged source loads of stem_fused.hip may read behind an image's last byte
+
+
+def image_pool(images: list[np.ndarray], T: int, device) -> tuple[torch.Tensor, torch.Tensor]:
+    """(ImageMeta records, uint8 pool) on ``device`` for the fused front ends: ``image_meta_bytes`` plus one more
+    256-byte pad block when fewer than POOL_SLACK pad bytes follow the last image (csrc/kernels/stem_fused.hip
+    stages source rows with whole aligned dwords and reads up to 7 bytes past a row's end)."""
+    meta, pool = image_meta_bytes(images, T)
+    if images and (-images[-1].size) % 256 < POOL_SLACK:
+        pool = np.concatenate([pool, np.zeros(256, np.uint8)])
+    meta_t = torch.frombuffer(bytearray(meta), dtype=torch.uint8).to(device)
+    return meta_t, torch.from_numpy(pool.copy()).to(device)
+
+
+def stem_fused_nhwc(pool: torch.Tensor, meta: torch.Tensor, ctrl: torch.Tensor, stem, *, S: int, act,
+                    out: torch.Tensor, crops: torch.Tensor | None = None, mean=None, inv_std=None,
+                    second=None, ir=None) -> torch.Tensor:
+    """bf16 front end as one kernel (csrc/kernels/stem_fused.hip), the four forms the planner emits:
+
+    * letterbox to ``S`` -> detector stem: ``stem`` = (w [16, 16, 3, 3] over the space-to-depth input, b);
+      ``out`` [cap, S/2, S/2, >= 16];
+    * the same -> 3x3 stride-2 conv: ``second`` = (w2 [32, 16, 3, 3], b2, act2); ``out`` [cap, S/4, S/4, >= 32],
+      S a multiple of 64;
+    * crop gather (``crops``: CropRef records, int32 [n, 8]; ``mean`` / ``inv_std``) -> classifier stem: ``stem`` =
+      (w [32, 16, 2, 2], b); ``out`` [cap, S/2, S/2, >= 32];
+    * the same -> MobileNetV2 block 1: ``ir`` = ((wd [32, 1, 3, 3], bd), (wp [16, 32, 1, 1], bp)); ``out``
+      [cap, S/2, S/2, >= 16], S a multiple of 32.
+
+    ``pool`` / ``meta``: ``image_pool``; ``ctrl``: ``ctrl_tensor`` (live images, live crops, crop base).  ``out``
+    is a contiguous bf16 tensor whose first extent is the batch capacity and whose last extent is the pixel stride:
+    items past the live count and channels past the form's are left as they are.  Weights are packed as the planner
+    packs them (pack_conv_weight, pack_ir_weights)."""
+    from ..engine.planner import pack_ir_weights
+
+    w, b = stem
+    if w.dim() != 4 or w.shape[1] != 16 or w.shape[2] != w.shape[3] or w.shape[0] % 16:
+        raise ValueError("stem_fused_nhwc: stem weights must be [Cout, 16, KS, KS] with Cout a multiple of 16")
+    if second is not None and ir is not None:
+        raise ValueError("stem_fused_nhwc: second (detector) and ir (classifier) exclude each other")
+    if (w.shape[2] != 3 or ir is not None) if crops is None else (w.shape[2] != 2 or second is not None):
+        raise ValueError("stem_fused_nhwc: the 3x3 stem (and second) letterbox images, the 2x2 stem (and ir) "
+                         "gathers crops")
+    if S <= 0 or S % 2:
+        raise ValueError("stem_fused_nhwc: S must be positive and even")
+    cout, ks = w.shape[0], w.shape[2]
+    if second is not None:
+        side, cdst = S // 4, second[0].shape[0]
+        if tuple(second[0].shape[1:]) != (cout, 3, 3):
+            raise ValueError("stem_fused_nhwc: second conv must be [C2, Cout, 3, 3]")
+    elif ir is not None:
+        (wd, _), (wp, _) = ir
+        side, cdst = S // 2, wp.shape[0]
+        if tuple(wd.shape) != (cout, 1, 3, 3) or tuple(wp.shape[1:]) != (cout, 1, 1):
+            raise ValueError("stem_fused_nhwc: fused block must be depthwise [Cout, 1, 3, 3] + project [C, Cout, 1, 1]")
+    else:
+        side, cdst = S // 2, cout
+    if (out.dim() != 4 or out.shape[1] != side or out.shape[2] != side or out.shape[3] < cdst or out.shape[3] % 4
+            or out.dtype != torch.bfloat16 or not out.is_contiguous() or out.device != pool.device):
+        raise ValueError(f"stem_fused_nhwc: out {tuple(out.shape)} {out.dtype} does not fit the form's output "
+                         f"[cap, {side}, {side}, >= {cdst} and a multiple of 4] bf16")
+    if pool.dtype != torch.uint8 or ctrl.dtype != torch.int32 or ctrl.numel() < 3:
+        raise ValueError("stem_fused_nhwc: pool must be uint8 and ctrl the int32 control block")
+    if crops is not None and (crops.dtype != torch.int32 or crops.dim() != 2 or crops.shape[1] != 8
+                              or not crops.is_contiguous()):
+        raise ValueError("stem_fused_nhwc: crops must be contiguous int32 [n, 8] CropRef records")
+    dev = pool.device
+    wt, bt, kpad, _ = pack_weights(w, b, dev, "bf16")[:4]
+    d = {"src": 0 if crops is None else 1, "pool": _ptr(pool), "meta": _ptr(meta), "ctrl": _ptr(ctrl),
+         "crops": _ptr(crops), "cap": out.shape[0], "S": S, "KS": ks, "w": _ptr(wt), "Kpad": kpad, "bias": _ptr(bt),
+         "Cout": cout, "act": ACT[act], "stream": _stream()}
+    if mean is not None:
+        d["mean"], d["inv_std"] = [float(v) for v in mean], [float(v) for v in inv_std]
+    keep = [wt, bt]
+    if second is not None:
+        w2, b2, act2 = second
+        w2t, b2t, kpad2, _ = pack_weights(w2, b2, dev, "bf16")[:4]
+        keep += [w2t, b2t]
+        d.update({"w2": _ptr(w2t), "Kpad2": kpad2, "bias2": _ptr(b2t), "Cout2": w2.shape[0], "act2": ACT[act2],
+                  "y2": _ptr(out), "y2s": out.shape[3]})
+    elif ir is not None:
+        pk = pack_ir_weights(None, ir[0], ir[1], cout)
+        irt = {"ir_wd": pk["wd"].to(torch.bfloat16), "ir_bd": pk["bd"].float(), "ir_wp": pk["wp"].to(torch.bfloat16),
+               "ir_bp": pk["bp"].float()}
+        irt = {k: v.contiguous().to(dev) for k, v in irt.items()}
+        keep += list(irt.values())
+        d.update({k: _ptr(v) for k, v in irt.items()})
+        d.update({"ir_y": _ptr(out), "ir_ys": out.shape[3]})
+    else:
+        d.update({"y": _ptr(out), "ys": out.shape[3]})
+    native().stem_fused(d)
+    torch.cuda.synchronize(dev)  # keep the packed weights alive until the kernel ran
+    del keep
+    return out
+
+
 def s2d_to_nchw(x: torch.Tensor) -> torch.Tensor:
     """[B, h, w, 16] space-to-depth (12 live channels) -> [B, 3, 2h, 2w] fp32."""
     B, h, w, _ = x.shape

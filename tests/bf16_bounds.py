@@ -1,6 +1,6 @@
 """Error bounds of the bf16 kernels against fp64 references, shared by test_bf16_bounds.py (CPU: proves the
-checks reject subtly wrong kernels), test_kernels_gpu.py and test_c3_fused_gpu.py.  A plain helper module,
-imported like detect_cases.py.
+checks reject subtly wrong kernels), test_kernels_gpu.py, test_c3_fused_gpu.py and test_stem_fused_gpu.py.  A plain
+helper module, imported like detect_cases.py.
 
 Two kinds of kernel, two checks.
 
@@ -15,8 +15,9 @@ absolute values, plus |bias| and |residual|) is the project's fp32 bound for the
 (test_fp32_gpu.py::_fp32_check), which also covers SiLU's v_exp / v_rcp.  No share of elements is exempt and a
 NaN fails (the maximum of a ratio is taken).  With an fp32 store the first term drops.
 
-**bf16 intermediates** (ir_block, ir_block_wave, ir_crop, the 14x14 whole-crop tile, c3_fused): the kernel
-stores intermediate tensors as bf16 in LDS.  ``assert_bf16_fused`` has three tiers over the same tensors:
+**bf16 intermediates** (ir_block, ir_block_wave, ir_crop, the 14x14 whole-crop tile, c3_fused, the two-stage front
+ends of stem_fused.hip): the kernel stores intermediate tensors as bf16 in LDS.  ``assert_bf16_fused`` has three
+tiers over the same tensors:
 
 1. every element: |got - exact64| <= bound64, ``exact64`` the block in fp64 without intermediate rounding,
    ``bound64`` the half-ulp error of every store propagated stage by stage through the absolute weights
@@ -30,9 +31,9 @@ stores intermediate tensors as bf16 in LDS.  ``assert_bf16_fused`` has three tie
 3. rms(got - mimic64) / rms(2^-8 mimic64) at most 1.5 x the same ratio of the CPU emulation (``rms_ref``): the tier
    that sees a small uniform error (a scaled bias, one wrong weight column), which tier 1's slack would hide.
 
-The emulation (``ir_emulate`` / ``c3_emulate``) is fp32 torch with bf16 rounding at the kernel's store points;
-tests compute its share and ratio on the CPU with the inputs they give the kernel.  ``MEASURED`` records them
-per fused case next to the kernels' values of one MI355X run.
+The emulation (``ir_emulate`` / ``c3_emulate`` / ``stem2_emulate``) is fp32 torch with bf16 rounding at the kernel's
+store points; tests compute its share and ratio on the CPU with the inputs they give the kernel.  ``MEASURED``
+records them per fused case next to the kernels' values of one MI355X run.
 """
 from __future__ import annotations
 
@@ -254,6 +255,36 @@ def c3_emulate(x: torch.Tensor, cv12, bottleneck, cv3, n: int, shortcut: bool) -
     return F.silu(F.conv2d(torch.cat([Tc, T2], 1), bf(cv3[0]), cv3[1].float())).to(torch.bfloat16)
 
 
+def stem2_refs(x: torch.Tensor, stem, second, act="silu", act2="silu"):
+    """Detector front end as stem2_kernel (stem_fused.hip) runs it on the bf16 s2d input ``x`` (NCHW [B, 16, H, W]):
+    T = act(conv3x3(x, w1) + b1) stored as bf16 in LDS, zero outside the map (the second conv pads T);
+    y = act2(conv3x3 stride 2 (T, w2) + b2), the bf16 output.  -> exact64, bound64, mimic64, tight64."""
+    x = x.double()
+    w1, b1 = bf64(stem[0]), stem[1].float().double()
+    w2, b2 = bf64(second[0]), second[1].float().double()
+    lip1 = LIP_SILU if act == "silu" else 1.0
+    lip2 = LIP_SILU if act2 == "silu" else 1.0
+    T = act64(F.conv2d(x, w1, b1, padding=1), act)
+    BT = _stage_bound(T, lip1 * FP32_REL * F.conv2d(x.abs(), w1.abs(), b1.abs(), padding=1))
+    y = act64(F.conv2d(T, w2, b2, stride=2, padding=1), act2)
+    By = _stage_bound(y, lip2 * (F.conv2d(BT, w2.abs(), stride=2, padding=1)
+                                 + FP32_REL * F.conv2d(T.abs() + BT, w2.abs(), b2.abs(), stride=2, padding=1)))
+    M = bf64(T)
+    mim = act64(F.conv2d(M, w2, b2, stride=2, padding=1), act2)
+    tight = HALF_ULP * mim.abs() + FP32_REL * F.conv2d(M.abs(), w2.abs(), b2.abs(), stride=2, padding=1) + 1e-30
+    return y, By, mim, tight
+
+
+def stem2_emulate(x: torch.Tensor, stem, second, act="silu", act2="silu", parts: bool = False):
+    """The CPU emulation of stem2_kernel: fp32 torch convs, bf16 rounding of the stem output (see ir_emulate for
+    the contiguous input).  -> NCHW bf16; ``parts``: (the fp32 output before its store, the stored stem output)."""
+    f = {"silu": F.silu, "relu6": F.relu6, None: lambda t: t}
+    x = x.float().contiguous()
+    T = bf(f[act](F.conv2d(x, bf(stem[0]), stem[1].float(), padding=1)))
+    y = f[act2](F.conv2d(T, bf(second[0]), second[1].float(), stride=2, padding=1))
+    return (y, T) if parts else y.to(torch.bfloat16)
+
+
 def c3_case(C1, ch, seed):
     """Weights and input of one C3 block (test_bf16_bounds.py, test_c3_fused_gpu.py): B 2, H 16, W 32 is 2 x 2
     tiles of 8 x 16."""
@@ -316,4 +347,10 @@ MEASURED: dict[str, tuple[float, float, float, float, float]] = {
     "ir_crop-split1-7-160-960-320-1-0": (0.00051, 0.4244, 0.000166, 0.4244, 0.079),
     "ir_tile(crop off)-7-160-960-320-1-0": (0.00051, 0.4244, 0.000166, 0.4244, 0.079),
     "ir_crop-split2-7-160-960-320-1-0": (0.00051, 0.4244, 0.000166, 0.4244, 0.079),
+    # the fused front ends (stem_fused.hip; test_stem_fused_gpu.py: stem2 = letterbox -> stem -> 3x3 s2 conv at S,
+    # stem_ir = crop gather -> stem -> block 1 at S; 10 live items)
+    "stem2-64": (0, 0.4394, 0, 0.4394, 0.334),
+    "stem2-192": (2.03e-05, 0.4187, 2.17e-05, 0.4187, 0.360),
+    "stem_ir-32": (4.88e-05, 0.4207, 9.77e-05, 0.4208, 0.255),
+    "stem_ir-96": (8.41e-05, 0.4197, 0, 0.4197, 0.293),
 }

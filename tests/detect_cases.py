@@ -8,6 +8,7 @@ import functools
 import numpy as np
 import torch
 
+import tie_image as ti
 from inference_arena_amd.models.yolov5nu import Detect
 from inference_arena_amd.ops import functional as AF
 from inference_arena_amd.postprocess import apply_nms
@@ -284,16 +285,19 @@ def crop_images():
     rng = np.random.default_rng(21)
     yy, xx = np.mgrid[0:450, 0:450]
     checker = np.repeat((((yy + xx) & 1) * 255).astype(np.uint8)[:, :, None], 3, 2)
-    return [checker, rng.integers(0, 256, (480, 640, 3), dtype=np.uint8),
+    # image 2: the tie image (tie_image.py) of a 464 -> 224 resize (scale 29/14 on both axes)
+    big = rng.integers(0, 256, (480, 640, 3), dtype=np.uint8)
+    return [checker, big, np.array(ti.tie_image(464, 464, 224, 224, 0, 1)),
             rng.integers(0, 256, (37, 53, 3), dtype=np.uint8)]
 
 
 # (image, x1, y1, x2, y2): w x h = 1x1, 1x40, 40x1, 2x2, 3x5, 223, 224 (the identity), 225, 448 (every tap at weight
 # 0.5: on the checkerboard, and on random pixels where the sums land on x.5 with even and odd x), a crop that ends
-# at the last row and column of the last image of the pool, and the two kinds of empty crop
-CROPS = [(1, 7, 9, 8, 10), (1, 601, 3, 602, 43), (1, 11, 470, 51, 471), (2, 51, 35, 53, 37), (2, 3, 5, 6, 10),
+# at the last row and column of the last image of the pool, the whole tie image (about 1,500 of its 150,528 resized
+# samples sit on a uint8 rounding tie of the host arithmetic), and the two kinds of empty crop
+CROPS = [(1, 7, 9, 8, 10), (1, 601, 3, 602, 43), (1, 11, 470, 51, 471), (3, 51, 35, 53, 37), (3, 3, 5, 6, 10),
          (1, 100, 50, 323, 273), (1, 416, 256, 640, 480), (1, 1, 2, 226, 227), (0, 1, 1, 449, 449),
-         (1, 33, 17, 481, 465), (2, 30, 20, 53, 37), (1, 50, 10, 50, 30), (2, 5, 30, 25, 12)]
+         (1, 33, 17, 481, 465), (3, 30, 20, 53, 37), (2, 0, 0, 464, 464), (1, 50, 10, 50, 30), (3, 5, 30, 25, 12)]
 
 
 def pack_crops(crops=CROPS):

@@ -228,3 +228,26 @@ def test_fused_accepts_the_emulated_c3_block(C1, ch, n, shortcut):
     bad[1, :, :, 15] = noconv[1, :, :, 15]  # the column left of the tile border at x = 16
     with pytest.raises(AssertionError, match="tier"):
         bb.assert_bf16_fused(bad, *refs, bb.flip_cap(flips), rms, what="3x3 dropped on a tile-border column")
+
+
+@pytest.mark.parametrize("H", [16, 32])
+def test_fused_accepts_the_emulated_two_stage_stem(H):
+    """stem2_refs / stem2_emulate (the detector front end of stem_fused.hip: a bf16 SiLU stem map in LDS, then the
+    3x3 stride-2 conv): the emulation passes the three tiers; a stem map that is not zeroed outside the S/2 map
+    (the second conv then reads stem values of padding instead of its own zero padding) fails them."""
+    g = torch.Generator().manual_seed(H)
+    x = bb.bf(torch.rand(2, 16, H, H, generator=g))
+    x[:, 12:] = 0
+    stem = (torch.randn(16, 16, 3, 3, generator=g) * 3 / 108 ** 0.5, torch.randn(16, generator=g) * 0.1)
+    second = (torch.randn(32, 16, 3, 3, generator=g) / 12, torch.randn(32, generator=g) * 0.1)
+    refs = bb.stem2_refs(x, stem, second)
+    y32, T = bb.stem2_emulate(x, stem, second, parts=True)
+    flips, rms = bb.fused_stats(bb.bf(y32), refs[2], refs[3])
+    r = bb.assert_bf16_fused(bb.bf(y32), *refs, bb.flip_cap(flips), rms, what=f"stem2 {H}")
+    assert r["worst"] < 0.7 and flips < 5e-4 and 0.3 < rms < 0.6, (r, flips, rms)
+    # the stem output of the padding ring is SiLU(bias), not zero
+    ring = F.pad(T, (1, 1, 1, 1)) + F.pad(torch.zeros_like(T), (1, 1, 1, 1), value=1.0) * \
+        bb.bf(F.silu(stem[1].float()))[None, :, None, None]
+    bad = F.silu(F.conv2d(ring, bb.bf(second[0]), second[1].float(), stride=2))
+    with pytest.raises(AssertionError, match="tier"):
+        bb.assert_bf16_fused(bb.bf(bad), *refs, bb.flip_cap(flips), rms, what="stem map not zeroed outside the map")

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import detect_cases as dc
+import tie_image as ti
 from inference_arena_amd.ops import functional as AF
 from inference_arena_amd.ops import native
 from inference_arena_amd.processing import MobileNetPreprocessor
@@ -412,7 +413,10 @@ def test_crop_gather_f32_equals_host(crop_env):
     assert (crop_env["grey"][8] == 128).all()
     x1, y1, x2, y2 = dc.CROPS[6][1:]
     assert np.array_equal(grey[6], crop_env["images"][1][y1:y2, x1:x2].transpose(2, 0, 1))
-    assert (crop_env["grey"][11:] == 0).all()  # the empty crops: extract_crop's 1x1 black
+    assert (crop_env["grey"][12:] == 0).all()  # the empty crops: extract_crop's 1x1 black
+    # the tie image's crop is made of samples where fused multiply-adds round to the neighbouring grey level
+    tie = crop_env["grey"][11].transpose(1, 2, 0)
+    assert dc.CROPS[11][0] == 2 and (tie != ti.resize_fused(crop_env["images"][2], 224, 224)).sum() >= 20
 
 
 def test_crop_gather_control_paths(crop_env):

@@ -14,6 +14,7 @@ import torch
 import torch.nn.functional as F
 
 import fp32_bounds as fb
+import tie_image as ti
 from inference_arena_amd.ops import functional as AF
 
 pytestmark = pytest.mark.gpu
@@ -481,12 +482,22 @@ def test_sppf_f32_exact(device):
         assert torch.equal(got[..., i * C:(i + 1) * C], ref.permute(0, 2, 3, 1)), i
 
 
+def _tie640():
+    """The tie image letterboxed to 640: 1344 x 84 resizes to 640 x 40 (scale 21/10 on both axes)."""
+    return np.array(ti.tie_image(1344, 84, 640, 40, 0, 1))
+
+
 def test_letterbox_f32_equals_host(device):
-    """Device letterbox in fp32 == the host reference preprocessor (uint8 rounding + /255), bit for bit."""
+    """Device letterbox in fp32 == the host reference preprocessor (uint8 rounding + /255), bit for bit.  The last
+    image is the tie image (tie_image.py; 1344 x 84 -> 640 x 40, scale 21/10): about 1,600 of its 76,800 resized
+    samples sit on a rounding tie of the host arithmetic, and at about 60 of them a fused multiply-add in the lerps or
+    the tap coordinate returns the neighbouring grey level (a random image has about one such sample per million), so
+    the `fp contract(off)` of letterbox.h is tested."""
     from inference_arena_amd.data.synthetic import synthetic_images
     from inference_arena_amd.processing import YOLOPreprocessor
 
     imgs = synthetic_images(2, 5) + synthetic_images(1, 6, hw=(333, 500)) + synthetic_images(1, 7, hw=(640, 427))
+    imgs.append(_tie640())
     out = AF.letterbox_s2d(imgs, 640, device, dtype=torch.float32)
     got = AF.s2d_to_nchw(out.cpu())
     pre = YOLOPreprocessor()
@@ -584,6 +595,7 @@ def test_fp32_letterbox_stem_matches_unfused(dense_models, device, monkeypatch):
     from inference_arena_amd.engine.planner import BUF_POOL, OP_CONV, OP_LETTERBOX
 
     imgs = synthetic_images(3, 71) + synthetic_images(1, 72, hw=(333, 500)) + synthetic_images(1, 73, hw=(640, 427))
+    imgs.append(_tie640())  # a sample rounded the other way by one of the two kernels is 1 / 255 in b0: far over 1e-5
     monkeypatch.setenv("ARENA_F32_STEM_S2", "0")  # this test pins the letterbox-sampling stem conv alone
     monkeypatch.setenv("ARENA_F32_LB_STEM", "0")
     plain = GpuPipeline(*dense_models, device=0, buckets=[8], share_buffers=False, dtype="fp32")
@@ -613,6 +625,7 @@ def test_fp32_stem_s2_fused_matches_unfused(dense_models, device, monkeypatch, t
     from inference_arena_amd.engine.planner import OP_STEMFUSED
 
     imgs = synthetic_images(3, 81) + synthetic_images(1, 82, hw=(333, 500)) + synthetic_images(1, 83, hw=(640, 427))
+    imgs.append(_tie640())
     monkeypatch.setenv("ARENA_STEM_X3_TH", th)
     monkeypatch.setenv("ARENA_F32_STEM_S2", "0")
     plain = GpuPipeline(*dense_models, device=0, buckets=[8], share_buffers=False, dtype="fp32")

@@ -13,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 import bf16_bounds as bb
+import tie_image as ti
 from inference_arena_amd.ops import functional as AF
 from inference_arena_amd.ops import native
 
@@ -222,6 +223,7 @@ def test_letterbox_matches_host(device):
     from inference_arena_amd.processing import letterbox
 
     imgs = synthetic_images(3, 5) + [np.random.default_rng(0).integers(0, 255, (300, 1000, 3), dtype=np.uint8)]
+    imgs.append(np.array(ti.tie_image(1344, 84, 640, 40, 0, 1)))  # resized samples on uint8 rounding ties
     out = AF.letterbox_s2d(imgs, 640, device)
     got = AF.s2d_to_nchw(out.cpu())
     for i, im in enumerate(imgs):
