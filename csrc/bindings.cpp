@@ -492,6 +492,7 @@ ExecutorConfig config_from(const py::dict& d) {
   c.cls_size = get<int>(d, "cls_size", c.cls_size);
   c.host_threads = get<int>(d, "host_threads", c.host_threads);
   c.raw_out_bytes = get<int64_t>(d, "raw_out_bytes", c.raw_out_bytes);
+  c.jpeg_ragged = get<bool>(d, "jpeg_ragged", c.jpeg_ragged);
   return c;
 }
 
@@ -845,6 +846,7 @@ PYBIND11_MODULE(_C, m) {
            py::arg("B"), py::arg("offsets"), py::arg("arena_bytes"), py::arg("impl") = py::none())
       .def("buckets", &Executor::buckets)
       .def("crop_cap_for", &Executor::crop_cap_for)
+      .def_property_readonly("jpeg_ragged", [](const Executor& e) { return e.config().jpeg_ragged; })
       .def("submit",
            [](Executor& e, const py::list& imgs) {
              std::vector<py::array> keep;
@@ -1016,7 +1018,18 @@ PYBIND11_MODULE(_C, m) {
   py::class_<EchoInstance, std::shared_ptr<EchoInstance>>(m, "EchoInstance")
       .def(py::init<int, int, int, int, int64_t, int64_t>(), py::arg("slots") = 2, py::arg("max_batch") = 32,
            py::arg("max_det") = 4, py::arg("latency_us") = 0, py::arg("staging_cap") = 0,
-           py::arg("raw_out_bytes") = 0);
+           py::arg("raw_out_bytes") = 0)
+      .def("set_record", &EchoInstance::set_record, py::arg("on"),
+           "Tests: keep the RGB pixels of every uint8 image submitted from now on (split-decoded JPEGs reconstructed).")
+      .def("take_recorded", [](EchoInstance& e) {
+        py::list out;
+        for (auto& r : e.take_recorded()) {
+          py::array_t<uint8_t> a({(py::ssize_t)r.h, (py::ssize_t)r.w, (py::ssize_t)3});
+          std::memcpy(a.mutable_data(), r.rgb.data(), r.rgb.size());
+          out.append(a);
+        }
+        return out;
+      }, "The recorded HxWx3 uint8 images in submission order; the record is emptied.");
 
   py::class_<DynamicBatcher>(m, "DynamicBatcher")
       .def(py::init([](py::list executors, const py::dict& cfg) {

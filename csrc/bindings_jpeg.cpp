@@ -249,7 +249,7 @@ void bind_jpeg(py::module& m) {
 
   m.def(
       "jpeg_decode_device",
-      [](std::vector<py::bytes> uploads, int device, bool guard, py::object progressive, bool compact) {
+      [](std::vector<py::bytes> uploads, int device, bool guard, py::object progressive, bool compact, bool ragged) {
         const int n = (int)uploads.size();
         const int prog = progressive_arg(progressive);
         std::vector<Parsed> ps(n);
@@ -290,6 +290,8 @@ void bind_jpeg(py::module& m) {
           max_blocks = std::max<int64_t>(max_blocks, descs[i].total_blocks);
           max_pix = std::max<int64_t>(max_pix, (int64_t)in.width * in.height);
         }
+        JpegRaggedPlan rplan;
+        if (ragged) rplan = jpeg_ragged_plan(descs.data(), n);
         py::list out;
         if (n == 0) return out;
         check(hipSetDevice(device), "hipSetDevice");
@@ -309,7 +311,12 @@ void bind_jpeg(py::module& m) {
               check(hipMemset(pool + rgb_off[i] - kGuard, kGuardByte, (size_t)kGuard), "guard");
               check(hipMemset(pool + rgb_off[i] + (int64_t)ps[i].info.width * ps[i].info.height * 3, kGuardByte, (size_t)kGuard), "guard");
             }
-          jpeg_reconstruct(dd, pool, n, (int)max_blocks, max_pix, nullptr, oriented);
+          if (ragged) {
+            if (oriented) throw std::invalid_argument("jpeg_decode_device: ragged=True takes no EXIF-oriented upload");
+            jpeg_reconstruct_ragged(dd, pool, n, rplan.idct_units, rplan.color_units, nullptr);
+          } else {
+            jpeg_reconstruct(dd, pool, n, (int)max_blocks, max_pix, nullptr, oriented);
+          }
           check(hipGetLastError(), "jpeg_reconstruct launch");
           check(hipDeviceSynchronize(), "jpeg_reconstruct");
           for (int i = 0; i < n; ++i) {
@@ -339,11 +346,49 @@ void bind_jpeg(py::module& m) {
         return out;
       },
       py::arg("uploads"), py::arg("device") = 0, py::arg("guard") = false, py::arg("progressive") = py::none(),
-      py::arg("compact") = false,
+      py::arg("compact") = false, py::arg("ragged") = false,
       "Entropy-decode on the host, reconstruct on the GPU (jpeg_idct.hip): list of HxWx3 uint8 in the EXIF\n"
       "orientation.  guard=True surrounds each RGB region with guard bytes and raises if the kernels touched them.\n"
       "progressive: accept SOF2 files (None = the process default).  compact=True ships the compact payload\n"
-      "(jpeg_decode_compact) instead of dense blocks.");
+      "(jpeg_decode_compact) instead of dense blocks.  ragged=True launches the ragged kernels\n"
+      "(jpeg_reconstruct_ragged; no EXIF-oriented upload) instead of the rectangular pair.");
+
+  m.def(
+      "jpeg_ragged_plan",
+      [](std::vector<py::bytes> uploads) {
+        const int n = (int)uploads.size();
+        std::vector<JpegDesc> descs(n);
+        int64_t max_blocks = 0, max_pix = 0;
+        for (int i = 0; i < n; ++i) {
+          const std::string s = uploads[i];
+          JpegInfo in;
+          std::string err;
+          if (jpeg_parse((const uint8_t*)s.data(), s.size(), in, err, 0, -1) != JpegStatus::Ok)
+            throw std::invalid_argument("upload " + std::to_string(i) + ": " + err);
+          descs[i] = jpeg_device_desc(in, 0, 0, 0);
+          max_blocks = std::max<int64_t>(max_blocks, descs[i].total_blocks);
+          max_pix = std::max<int64_t>(max_pix, (int64_t)in.width * in.height);
+        }
+        const JpegRaggedPlan p = jpeg_ragged_plan(descs.data(), n);
+        py::list fi, fc;
+        for (int i = 0; i < n; ++i) {
+          fi.append(descs[i].pad_[0]);
+          fc.append(descs[i].pad_[1]);
+        }
+        py::dict out;
+        out["idct_first"] = fi;
+        out["color_first"] = fc;
+        out["idct_units"] = p.idct_units;
+        out["color_units"] = p.color_units;
+        // the grids of jpeg_reconstruct over the same batch
+        out["rect_idct_units"] = (int64_t)n * ((max_blocks + kJpegBlocksPerUnit - 1) / kJpegBlocksPerUnit);
+        out["rect_color_units"] = n == 0 ? (int64_t)0 : (int64_t)n * std::max<int64_t>(1, (max_pix + 1023) / 1024);
+        return out;
+      },
+      py::arg("uploads"),
+      "Launch plan of the ragged reconstruction over a batch of uploads (host only; headers are parsed, nothing is\n"
+      "decoded): dict(idct_first, color_first = each upload's first unit, idct_units, color_units = the ragged grids,\n"
+      "rect_idct_units, rect_color_units = the workgroups the rectangular pair launches for the same batch).");
   // ---- crop encoder ----
   m.attr("SIZEOF_JPEG_ENC_DESC") = (int)sizeof(JpegEncDesc);
 
@@ -401,8 +446,10 @@ void bind_jpeg(py::module& m) {
 
   m.def(
       "jpeg_encode_device",
-      [](U8Array frame, py::object boxes, int device, int64_t capacity_bytes) {
-        return encode_device(frame, boxes, device, capacity_bytes, false)["blobs"];
+      [](U8Array frame, py::object boxes, int device, int64_t capacity_bytes) -> py::object {
+        // the dict outlives the lookup: an item accessor of a temporary dict would be read after the dict is gone
+        const py::dict out = encode_device(frame, boxes, device, capacity_bytes, false);
+        return out["blobs"];
       },
       py::arg("frame"), py::arg("boxes"), py::arg("device") = 0, py::arg("capacity_bytes") = 0,
       "Upload an HxWx3 uint8 frame and encode the crops of `boxes` (x1, y1, x2, y2 floats, clipped like\n"

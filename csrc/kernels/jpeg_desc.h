@@ -24,8 +24,8 @@ struct JpegDesc {
   int32_t ncomp, layout, width, height;
   int32_t total_blocks;  // sum over components of bw * bh
   int32_t orientation;   // EXIF orientation 1..8 of the output (0 reads as 1): see jpeg_idct.hip for the placement
-  int32_t pad_[2];
-  int64_t rgb_off;       // packed RGB output in the oriented geometry (the ImageMeta offset the pipeline reads)
+  int32_t pad_[2];       // ragged launch only (jpeg_ragged_plan below): first IDCT unit, first colour unit; else 0
+  int64_t rgb_off;      // packed RGB output in the oriented geometry (the ImageMeta offset the pipeline reads)
   JpegCompDesc comp[kJpegMaxComp];
   uint16_t qt[kJpegMaxComp][64];  // dequantization table per component, natural order
   // compact payload (runtime/jpeg_decode.h jpeg_decode_compact; comp[].coef_off unused): per block a uint64
@@ -34,5 +34,35 @@ struct JpegDesc {
   int32_t compact, pad2_;
 };
 static_assert(sizeof(JpegDesc) == 576, "JpegDesc layout is shared with the kernels");
+
+// Ragged launch of the reconstruction (jpeg_reconstruct_ragged, jpeg_idct.hip): a 1-D grid with one workgroup per
+// unit of real work, where the rectangular launch sizes every image's share by the largest image of the batch.
+// A unit is up to kJpegBlocksPerUnit 8x8 blocks of one image for the IDCT, and up to kJpegQuadsPerUnit 4-pixel row
+// quads (ceil(width / 4) per row) of one image for the colour pass.
+constexpr int kJpegBlocksPerUnit = 32;
+constexpr int kJpegQuadsPerUnit = 256;
+
+inline int jpeg_idct_units(const JpegDesc& d) { return (d.total_blocks + kJpegBlocksPerUnit - 1) / kJpegBlocksPerUnit; }
+inline int jpeg_color_units(const JpegDesc& d) {
+  const int64_t quads = (int64_t)((d.width + 3) >> 2) * d.height;
+  return (int)((quads + kJpegQuadsPerUnit - 1) / kJpegQuadsPerUnit);
+}
+
+struct JpegRaggedPlan {
+  int idct_units = 0, color_units = 0;  // grid sizes of the two ragged kernels
+};
+
+// Write each descriptor's first IDCT unit and first colour unit (exclusive prefix sums over the batch, so both
+// sequences are monotone) into pad_[0] / pad_[1], where a workgroup of the ragged kernels searches for its image.
+inline JpegRaggedPlan jpeg_ragged_plan(JpegDesc* descs, int n) {
+  JpegRaggedPlan p;
+  for (int i = 0; i < n; ++i) {
+    descs[i].pad_[0] = p.idct_units;
+    descs[i].pad_[1] = p.color_units;
+    p.idct_units += jpeg_idct_units(descs[i]);
+    p.color_units += jpeg_color_units(descs[i]);
+  }
+  return p;
+}
 
 }  // namespace arena

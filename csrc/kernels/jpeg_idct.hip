@@ -16,6 +16,10 @@
 // the two kernels above.  The oriented kernel computes each quad with the same color_quad and only places it
 // differently (see its comment), so its pixels are those of the plain kernel, moved.
 //
+// jpeg_reconstruct_ragged launches the same two stages as jpeg_idct_ragged_kernel and jpeg_color_ragged_kernel over
+// 1-D grids with one workgroup per unit of real work, for batches of crops of very different sizes (see "ragged
+// launch" below); same arithmetic, same bytes.
+//
 // The arithmetic is kernels/jpeg_math.h, the same functions the host reference (jpeg_coefs_to_rgb) uses, so
 // the result is bit-identical to it and to PIL / libjpeg-turbo (tests/test_jpeg_native_gpu.py).  The work is
 // a few MB of traffic per batch of 32 frames: latency, not throughput, is what the layout optimises (every
@@ -412,7 +416,170 @@ __global__ __launch_bounds__(256) void jpeg_color_oriented_kernel(const JpegDesc
   }
 }
 
+// ---- ragged launch -----------------------------------------------------------------------------------------------
+//
+// The two kernels above run over (units of the largest image) x (images): right for a batch of similar uploads, but
+// in a batch of arm B's crops, whose sizes spread over two orders of magnitude, almost every workgroup reads a
+// descriptor and exits.  The ragged kernels run over a 1-D grid with one workgroup per unit of real work
+// (jpeg_desc.h: 32 blocks of one image, 256 row quads of one image); the descriptors carry the exclusive prefix of
+// the unit counts (pad_[0] IDCT, pad_[1] colour, written by jpeg_ragged_plan).  They are separate kernels after the
+// ones above, whose code objects stay as they are; the per-block and per-quad code is the same, as functions.
+static_assert(kJpegBlocksPerUnit == kBlocksPerGroup && kJpegQuadsPerUnit == 256, "unit sizes are the workgroup's");
+
+// Image of unit u: the last descriptor whose first unit is <= u.  The prefix is monotone, so that is the number of
+// descriptors with first unit <= u, less one.  The workgroup counts them 256 at a time, one load per lane (each
+// descriptor is a cache line of its own, so a batch of 128 costs the workgroup 128 lines, read once) and a ballot
+// per wave; the four partial counts meet in LDS (`part`, 4 ints).  No dependent chain of loads.  The result is
+// uniform over the workgroup; first[0] = 0 <= u, so it is >= 0 for every unit of the grid.
+template <int kField>
+__device__ __forceinline__ int ragged_image(const JpegDesc* __restrict__ descs, int n, int u, int* part) {
+  int count = 0;
+  for (int base = 0; base < n; base += 256) {
+    const int i = base + (int)threadIdx.x;
+    const bool below = i < n && descs[i].pad_[kField] <= u;
+    count += __popcll(__ballot(below));
+  }
+  if (((int)threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = count;
+  __syncthreads();
+  return __builtin_amdgcn_readfirstlane(part[0] + part[1] + part[2] + part[3]) - 1;
+}
+
+// Blocks group * 32 .. group * 32 + 31 of image d: the body of jpeg_idct_kernel (same loads, same LDS layout, same
+// jpeg_math.h calls), with the group and the descriptor as arguments.
+__device__ __forceinline__ void idct_group(const JpegDesc& d, uint8_t* __restrict__ pool, int group,
+                                           int32_t (*ws)[8][9]) {
+  const int g = threadIdx.x >> 3, l = threadIdx.x & 7;
+  const int blk = group * kBlocksPerGroup + g;
+  const bool live = blk < d.total_blocks;
+  int c = 0, b = blk;
+  const int n0 = d.comp[0].bw * d.comp[0].bh;
+  if (d.ncomp > 1 && b >= n0) {
+    c = 1;
+    b -= n0;
+    const int n1 = d.comp[1].bw * d.comp[1].bh;
+    if (b >= n1) {
+      c = 2;
+      b -= n1;
+    }
+  }
+  const JpegCompDesc& cd = d.comp[c];
+  int32_t row[8];
+  if (live && d.compact) {
+    const uint64_t mask = reinterpret_cast<const uint64_t*>(pool + d.cmask_off)[blk];
+    const int32_t v0 = (int32_t)reinterpret_cast<const uint32_t*>(pool + d.cvoff_off)[blk];
+    const int16_t* vals = reinterpret_cast<const int16_t*>(pool + d.cval_off);
+    const uint4 qv = *reinterpret_cast<const uint4*>(&d.qt[c][l * 8]);
+    const uint32_t qw[4] = {qv.x, qv.y, qv.z, qv.w};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int z = (int)((kZigzagCol[k] >> (8 * l)) & 0xFF);
+      const int idx = v0 + __popcll(mask & ((1ull << z) - 1ull));
+      int32_t cf = 0;
+      if ((mask >> z) & 1ull) cf = (int32_t)vals[idx];  // zero coefficients issue no load
+      const int32_t q = (int32_t)((k & 1) ? (qw[k >> 1] >> 16) : (qw[k >> 1] & 0xFFFF));
+      row[k] = cf * q;
+    }
+  } else if (live) {
+    const uint4 cv = *reinterpret_cast<const uint4*>(pool + cd.coef_off + (int64_t)b * 128 + l * 16);
+    const uint4 qv = *reinterpret_cast<const uint4*>(&d.qt[c][l * 8]);
+    const uint32_t cw[4] = {cv.x, cv.y, cv.z, cv.w}, qw[4] = {qv.x, qv.y, qv.z, qv.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      row[2 * k] = (int32_t)(int16_t)(cw[k] & 0xFFFF) * (int32_t)(qw[k] & 0xFFFF);
+      row[2 * k + 1] = (int32_t)(int16_t)(cw[k] >> 16) * (int32_t)(qw[k] >> 16);
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) row[k] = 0;
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) ws[g][l][k] = row[k];
+  __syncthreads();
+  // pass 1: column l
+  int32_t v[8], o[8];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) v[r] = ws[g][r][l];
+  jpegm::idct8<int32_t>(v, o, jpegm::kPass1Shift);
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < 8; ++r) ws[g][r][l] = o[r];
+  __syncthreads();
+  // pass 2: row l -> 8 samples
+#pragma unroll
+  for (int k = 0; k < 8; ++k) v[k] = ws[g][l][k];
+  jpegm::idct8<int32_t>(v, o, jpegm::kPass2Shift);
+  if (!live) return;
+  uint32_t lo = 0, hi = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    lo |= (uint32_t)jpegm::idct_sample<int32_t>(o[k]) << (8 * k);
+    hi |= (uint32_t)jpegm::idct_sample<int32_t>(o[k + 4]) << (8 * k);
+  }
+  const int by = b / cd.bw, bx = b - by * cd.bw;
+  const int64_t stride = (int64_t)cd.bw * 8;
+  uint2* dst = reinterpret_cast<uint2*>(pool + cd.plane_off + (int64_t)(by * 8 + l) * stride + bx * 8);
+  *dst = make_uint2(lo, hi);
+}
+
+__global__ __launch_bounds__(256) void jpeg_idct_ragged_kernel(const JpegDesc* __restrict__ descs,
+                                                               uint8_t* __restrict__ pool, int n_images) {
+  __shared__ int32_t ws[kBlocksPerGroup][8][9];  // jpeg_idct_kernel's layout
+  __shared__ int part[4];
+  const int u = (int)blockIdx.x;
+  const int img = ragged_image<0>(descs, n_images, u, part);
+  if (img < 0) return;  // never for a grid of jpeg_ragged_plan's size; uniform over the workgroup
+  const JpegDesc& d = descs[img];
+  idct_group(d, pool, u - d.pad_[0], ws);
+}
+
+// Quads unit * 256 .. unit * 256 + 255 of an image's rows x quads, one per lane: color_quad and jpeg_color_kernel's
+// stores.  The units of an image cover its ceil(W / 4) * H quads exactly, so there is no grid-stride loop.
+__global__ __launch_bounds__(256) void jpeg_color_ragged_kernel(const JpegDesc* __restrict__ descs,
+                                                                uint8_t* __restrict__ pool, int n_images) {
+  __shared__ int part[4];
+  const int u = (int)blockIdx.x;
+  const int img = ragged_image<1>(descs, n_images, u, part);
+  if (img < 0) return;
+  const JpegDesc& d = descs[img];
+  const int W = d.width, H = d.height, layout = d.layout;
+  const int qpr = (W + 3) >> 2;  // quads per row
+  const int total = qpr * H;
+  const int t = (u - d.pad_[1]) * 256 + (int)threadIdx.x;
+  if (t >= total) return;
+  const uint8_t* yp = pool + d.comp[0].plane_off;
+  const int ys = d.comp[0].bw * 8;
+  const int y = t / qpr, q = t - y * qpr;
+  const int x0 = 4 * q;
+  const int n = min(4, W - x0);
+  uint8_t px[12];
+  color_quad(d, pool, yp, ys, layout, y, q, px);
+  uint8_t* out = pool + d.rgb_off + ((int64_t)y * W + x0) * 3;
+  if (n == 4 && (W & 3) == 0) {
+    uint32_t w[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      w[k] = (uint32_t)px[4 * k] | ((uint32_t)px[4 * k + 1] << 8) | ((uint32_t)px[4 * k + 2] << 16) |
+             ((uint32_t)px[4 * k + 3] << 24);
+    uint32_t* o32 = reinterpret_cast<uint32_t*>(out);
+    o32[0] = w[0];
+    o32[1] = w[1];
+    o32[2] = w[2];
+  } else {
+    for (int k = 0; k < 3 * n; ++k) out[k] = px[k];
+  }
+}
+
 }  // namespace
+
+void jpeg_reconstruct_ragged(const JpegDesc* d_descs, uint8_t* d_pool, int n_images, int idct_units, int color_units,
+                             hipStream_t s) {
+  if (n_images <= 0) return;
+  if (idct_units > 0)
+    hipLaunchKernelGGL(jpeg_idct_ragged_kernel, dim3((unsigned)idct_units), dim3(256), 0, s, d_descs, d_pool, n_images);
+  if (color_units > 0)
+    hipLaunchKernelGGL(jpeg_color_ragged_kernel, dim3((unsigned)color_units), dim3(256), 0, s, d_descs, d_pool,
+                       n_images);
+}
 
 void jpeg_reconstruct(const JpegDesc* d_descs, uint8_t* d_pool, int n_images, int max_blocks, int64_t max_pixels,
                       hipStream_t s, bool oriented) {

@@ -536,6 +536,12 @@ void stamp(void* dst, hipStream_t s);
 struct JpegDesc;
 void jpeg_reconstruct(const JpegDesc* d_descs, uint8_t* d_pool, int n_images, int max_blocks, int64_t max_pixels,
                       hipStream_t s, bool oriented = false);
+// The same reconstruction over a ragged grid: one workgroup per unit of real work (jpeg_desc.h), for batches whose
+// image sizes differ widely (arm B's crops).  The descriptors carry their first units (jpeg_ragged_plan, which also
+// gives the two totals); no descriptor may have an EXIF orientation other than 1.  Writes the bytes jpeg_reconstruct
+// writes.
+void jpeg_reconstruct_ragged(const JpegDesc* d_descs, uint8_t* d_pool, int n_images, int idct_units, int color_units,
+                             hipStream_t s);
 
 // Device half of the JPEG crop encoder (csrc/kernels/jpeg_fdct.hip): for n_crops descriptors (jpeg_enc_desc.h)
 // read each crop from the packed RGB frame at d_frame and write its quantised 4:2:0 coefficient blocks (int16,

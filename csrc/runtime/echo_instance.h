@@ -74,6 +74,10 @@ class EchoInstance : public BatchInstance {
         std::vector<int16_t> dense;
         jpeg_coefs_to_rgb(*imgs[i].jpeg, jpeg_dense_coefs(*imgs[i].jpeg, imgs[i].data, dense), rgb.data());
         first = rgb[0];
+        if (record_) recorded_.push_back({imgs[i].h, imgs[i].w, std::move(rgb)});
+      } else if (record_ && imgs[i].bytes <= 0) {
+        recorded_.push_back({imgs[i].h, imgs[i].w,
+                             std::vector<uint8_t>(imgs[i].data, imgs[i].data + (size_t)imgs[i].h * imgs[i].w * 3)});
       }
       const int k_n = std::min(max_det_, 1 + first % max_det_);
       r.det_count[i] = k_n;
@@ -135,7 +139,26 @@ class EchoInstance : public BatchInstance {
     return std::move(results_[slot]);
   }
 
+  // Tests: keep the RGB pixels of every uint8 image submitted from now on (a split-decoded JPEG as reconstructed
+  // above), in submission order; take_recorded() hands them out and forgets them.
+  struct Recorded {
+    int h, w;
+    std::vector<uint8_t> rgb;
+  };
+  void set_record(bool on) {
+    std::lock_guard<std::mutex> lk(mu_);
+    record_ = on;
+  }
+  std::vector<Recorded> take_recorded() {
+    std::lock_guard<std::mutex> lk(mu_);
+    std::vector<Recorded> out;
+    out.swap(recorded_);
+    return out;
+  }
+
  private:
+  bool record_ = false;
+  std::vector<Recorded> recorded_;
   int slots_, max_batch_, max_det_, latency_us_;
   int64_t staging_cap_, raw_out_bytes_;
   std::vector<BatchResult> results_;

@@ -1263,6 +1263,11 @@ int Executor::submit(const std::vector<InputImage>& imgs) {
     ++nj;
     off = end;
   }
+  // ragged launch (cfg_.jpeg_ragged): the descriptors carry their first units; an oriented batch keeps the
+  // rectangular pair (there is no oriented ragged kernel), and then, as with the flag off, the fields stay 0
+  const bool ragged = cfg_.jpeg_ragged && nj > 0 && !oriented;
+  JpegRaggedPlan rplan;
+  if (ragged) rplan = jpeg_ragged_plan(jdesc, nj);
   {
     trace::Range tp("arena.pack");
     // timing experiments only: ARENA_DEBUG_SKIP_PACK=n reuses the staged pixels after the first n batches
@@ -1287,8 +1292,12 @@ int Executor::submit(const std::vector<InputImage>& imgs) {
   // split-decoded JPEGs: dequantize + IDCT + upsample + colour-convert into their RGB slots before the program
   if (nj > 0) {
     trace::Range tj("arena.jpeg_reconstruct");
-    jpeg_reconstruct((const JpegDesc*)(sl.d_in + jpeg_desc_off()), sl.d_in + in_bytes_meta(), nj, max_blocks, max_pix,
-                     sl.stream, oriented);
+    if (ragged)
+      jpeg_reconstruct_ragged((const JpegDesc*)(sl.d_in + jpeg_desc_off()), sl.d_in + in_bytes_meta(), nj,
+                              rplan.idct_units, rplan.color_units, sl.stream);
+    else
+      jpeg_reconstruct((const JpegDesc*)(sl.d_in + jpeg_desc_off()), sl.d_in + in_bytes_meta(), nj, max_blocks, max_pix,
+                       sl.stream, oriented);
     ARENA_HIP_CHECK(hipGetLastError());
   }
   // frames exported to another buffer on this device (arm B's IPC ring): device to device, in stream order

@@ -122,6 +122,9 @@ struct ExecutorConfig {
   int cls_size = 224;
   int host_threads = 8;
   int64_t raw_out_bytes = 0;  // per-image raw output region (reference tensor contracts)
+  // Split-decoded JPEGs of a batch without EXIF orientations are reconstructed over the ragged grid
+  // (jpeg_reconstruct_ragged): for batches of many crops of very different sizes (arm B's classification service)
+  bool jpeg_ragged = false;
 };
 
 struct BucketInfo {

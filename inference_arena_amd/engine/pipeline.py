@@ -87,7 +87,7 @@ class GpuProgramRunner:
     def __init__(self, program, *, device: int = 0, buckets=None, max_det: int | None = None,
                  crop_cap_per_image: int | None = None, host_threads: int | None = None,
                  pool_bytes_per_image: int = 640 * 640 * 3, weights: np.ndarray | None = None,
-                 share_buffers: bool = True):
+                 share_buffers: bool = True, jpeg_ragged: bool = False):
         gcfg = get_gpu_config()
         self.program = program
         self.buckets = sorted(int(b) for b in (buckets or gcfg["batch_buckets"]))
@@ -105,6 +105,8 @@ class GpuProgramRunner:
             "cls_size": int(program.meta.get("cls_size", 224)),
             "host_threads": int(host_threads or gcfg["host_threads"]),
             "raw_out_bytes": self.raw_out_bytes,
+            # split-decoded JPEGs reconstructed over a ragged grid (csrc/kernels/jpeg_idct.hip): batches of crops
+            "jpeg_ragged": bool(jpeg_ragged),
         })
         if weights is not None and weights.nbytes != program.weights.nbytes:
             raise ValueError("weight blob does not match the program's layout")

@@ -60,7 +60,7 @@ def build_session(kind: str, yolo=None, mnet=None, *, device: int = 0, buckets=N
     if kind == "detector":
         return GpuDetector(yolo, device=device, **common)
     if kind == "classifier":
-        return GpuClassifier(mnet, device=device, **common)
+        return GpuClassifier(mnet, device=device, **common, **kw)
     if kind == "frame_classifier":
         return GpuFrameClassifier(mnet, device=device, **common, **kw)
     if kind == "split":

@@ -9,7 +9,10 @@ in-band in ``error``; ``ClassifyBatch`` loops over ``Classify``).
 MI355X design: every RPC only decodes (thread pool) and enqueues its crop
 into the GPU classifier's dynamic batcher, so crops of concurrent requests —
 and all crops of one ``ClassifyBatch`` — run as one batched MobileNetV2 graph
-replay.  ``Health/Check`` is implemented (declared only upstream), and with
+replay.  With ``ARENA_CROP_DECODE=gpu`` a JPEG crop is not decoded here at all:
+its bytes go to the backend's ``classify_bytes`` (split decoder: Huffman on C++
+threads, pixels reconstructed on the GPU inside the batch, the same pixels).
+``Health/Check`` is implemented (declared only upstream), and with
 ``ARENA_INFER_SERVICE=1`` so is ``InferenceService/Infer`` (also declared
 only upstream; see server/inference_service.py).  With
 ``ARENA_CROP_TRANSPORT=device`` requests may name a frame in the detection
@@ -39,13 +42,16 @@ from .service_backends import ClassifierBackend, build_classifier_backend
 log = logging.getLogger("arena.classification")
 
 MAX_MESSAGE = 50 * 1024 * 1024
+JPEG_SOI = b"\xff\xd8"
 GRPC_OPTIONS = [("grpc.max_send_message_length", MAX_MESSAGE), ("grpc.max_receive_message_length", MAX_MESSAGE)]
 
 
 class ClassificationServicer:
-    def __init__(self, backend: ClassifierBackend, labels: list[str], decode_threads: int = 8):
+    def __init__(self, backend: ClassifierBackend, labels: list[str], decode_threads: int = 8,
+                 crop_decode: str = "pil"):
         self.backend = backend
         self.labels = labels
+        self.crop_decode = crop_decode  # ARENA_CROP_DECODE: pil | gpu (JPEG crops only, backends with classify_bytes)
         self.pool = ThreadPoolExecutor(max_workers=max(1, decode_threads), thread_name_prefix="crop-decode")
         self.n_requests = 0
         self.n_errors = 0
@@ -90,6 +96,10 @@ class ClassificationServicer:
                     out[i] = self._response(rid, res[j][0], res[j][1], t0, t1, t2)
         return out
 
+    async def _decode(self, data: bytes):
+        """PIL decode of an encoded crop on the thread pool."""
+        return await asyncio.get_running_loop().run_in_executor(self.pool, decode_crop, data)
+
     async def Classify(self, request, context=None):
         t0 = time.perf_counter()
         request_id_var.set(request.request_id)
@@ -100,8 +110,15 @@ class ClassificationServicer:
             data = request.image_crop
             if data[:4] == RAW_MAGIC:  # raw crops are a header + a view: no codec, no thread hop
                 crop = decode_crop(data)
+            elif self.crop_decode == "gpu" and data[:2] == JPEG_SOI and hasattr(self.backend, "classify_bytes"):
+                # ARENA_CROP_DECODE=gpu: the bytes go to the split decoder (Huffman on C++ threads, pixels
+                # reconstructed inside the classifier batch); what it hands back takes _decode below
+                t1 = time.perf_counter()
+                idx, _logit, prob = await self.backend.classify_bytes(data, self._decode)
+                t2 = time.perf_counter()
+                return self._response(request.request_id, idx.tolist(), prob.tolist(), t0, t1, t2)
             else:
-                crop = await asyncio.get_running_loop().run_in_executor(self.pool, decode_crop, data)
+                crop = await self._decode(data)
             t1 = time.perf_counter()
             idx, _logit, prob = await self.backend.classify(crop)
             t2 = time.perf_counter()
@@ -156,7 +173,8 @@ async def start_server(settings: Settings, backend: ClassifierBackend | None = N
     server also answers ``inference.InferenceService/Infer`` (server/inference_service.py)."""
     backend = backend or build_classifier_backend(settings)
     labels = load_labels(settings.LABELS_FILE or None)
-    servicer = ClassificationServicer(backend, labels, settings.ARENA_DECODE_THREADS)
+    servicer = ClassificationServicer(backend, labels, settings.ARENA_DECODE_THREADS,
+                                      crop_decode=settings.ARENA_CROP_DECODE)
     if frames is None and settings.ARENA_CROP_TRANSPORT == "device" and settings.ARENA_DEVICE != "cpu":
         from .service_backends import build_frame_classifier
 

@@ -24,6 +24,12 @@ import numpy as np
 from .batching import AsyncBatcher
 
 
+# Launch of the JPEG reconstruction in the classifier sessions of ARENA_CROP_DECODE=gpu: the ragged kernels, unless
+# their summed duration over a batch of 128 workload crops exceeds the rectangular pair's by more than the repeats'
+# spread (the rule and the measurement: profiles/crop_decode/README.md).
+CROP_DECODE_RAGGED = True
+
+
 def _default_buckets(max_batch: int) -> list[int]:
     return sorted({b for b in (1, 2, 4, 8, 16, 32, 64, max_batch) if b <= max_batch})
 
@@ -51,12 +57,14 @@ class GpuClassifierBackend(ClassifierBackend):
 
     def __init__(self, mnet, *, device: int = 0, instances: int = 1, max_batch: int = 64,
                  max_queue_delay_us: int = 300, preferred: list[int] | None = None,
-                 devices: list[int] | None = None, idle_queue_delay_us: int = -1):
+                 devices: list[int] | None = None, idle_queue_delay_us: int = -1, jpeg_ragged: bool = False):
         from ..engine.registry import build_session
 
         bk = _default_buckets(max_batch)
         self.devices = [int(d) for d in (devices or [device])]
-        self.runners = [build_session("classifier", mnet=mnet, device=d, buckets=bk)
+        # jpeg_ragged: crops arriving as JPEG bytes (classify_bytes) are reconstructed over the ragged grid
+        kw = {"jpeg_ragged": True} if jpeg_ragged else {}
+        self.runners = [build_session("classifier", mnet=mnet, device=d, buckets=bk, **kw)
                         for d in self.devices for _ in range(instances)]
         self.batcher = AsyncBatcher(self.runners, max_batch=max_batch, preferred=preferred,
                                     max_queue_delay_us=max_queue_delay_us, idle_queue_delay_us=idle_queue_delay_us)
@@ -72,8 +80,20 @@ class GpuClassifierBackend(ClassifierBackend):
         d = await self.batcher.run(np.ascontiguousarray(crop, dtype=np.uint8))
         return d["topk_idx"][0], d["topk_logit"][0], d["topk_prob"][0]
 
+    async def classify_bytes(self, data: bytes, decode):
+        """A JPEG crop through the native split decoder (``ARENA_CROP_DECODE=gpu``): Huffman decode on C++ threads,
+        pixels reconstructed on the GPU inside the classifier batch, the same pixels PIL decodes.  Crops the
+        decoder hands back (progressive with the switch off, CMYK, subsampled crops no wider than 4 pixels, any
+        other format) go through ``await decode(data)`` and ``classify``'s path; a corrupt crop raises."""
+        d = await self.batcher.run_jpeg(data, decode, threads=int(os.environ.get("ARENA_INGEST_THREADS", "4")))
+        return d["topk_idx"][0], d["topk_logit"][0], d["topk_prob"][0]
+
     def stats(self) -> dict:
-        return self.batcher.stats()
+        st = self.batcher.stats()
+        ing = self.batcher.ingest_stats()  # None until the first classify_bytes
+        if ing is not None:
+            st["ingest"] = ing  # native / fallback / errors / progressive_decoded / cpu_decode_ms
+        return st
 
     def close(self) -> None:
         self.batcher.close()
@@ -232,7 +252,11 @@ def build_classifier_backend(settings) -> ClassifierBackend:
                                 max_queue_delay_us=int(os.environ.get("ARENA_CLS_QUEUE_DELAY_US", "2000")),
                                 # while no batch is in flight the detection side's short delay applies, so a lone
                                 # request is not held for 2 ms (1 user: P50 6.8 ms with 2 ms, 5.1 ms with 0.5 ms)
-                                idle_queue_delay_us=int(settings.ARENA_QUEUE_DELAY_US))
+                                idle_queue_delay_us=int(settings.ARENA_QUEUE_DELAY_US),
+                                # ARENA_CROP_DECODE=gpu: a batch holds up to 128 JPEG crops whose sizes spread over
+                                # two orders of magnitude, so the reconstruction runs over the ragged grid
+                                # (profiles/crop_decode/README.md)
+                                jpeg_ragged=CROP_DECODE_RAGGED and settings.ARENA_CROP_DECODE == "gpu")
 
 
 def build_frame_classifier(settings):

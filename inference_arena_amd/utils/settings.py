@@ -57,6 +57,9 @@ class Settings(BaseModel):
     ARENA_CROP_TRANSPORT: str = "jpeg"  # jpeg (reference) | png | raw | device (IPC frame hand-off)
     ARENA_DEVICE_RING_SLOTS: int = 512  # device transport: frames in flight per detection process
     ARENA_CROP_ENCODE: str = "pil"      # jpeg crops: pil (reference, host) | gpu (split encoder, server/crop_codec.py)
+    # jpeg crops on the classification side: pil (reference, thread-pool decode) | gpu (split decoder: Huffman on C++
+    # threads, IDCT + colour inside the classifier batch; GpuClassifierBackend.classify_bytes)
+    ARENA_CROP_DECODE: str = "pil"
     ARENA_FANOUT: str = "parallel"      # parallel (one Classify per crop, reference) | batch (one ClassifyBatch)
     ARENA_GATEWAY_MODE: str = "pipeline"  # pipeline (one fused ensemble RPC) | tensor (reference per-model RPCs)
     ARENA_INSTANCES: int = 1            # executor instances per GPU behind one batcher
