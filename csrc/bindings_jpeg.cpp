@@ -2,8 +2,8 @@
 // entropy decoder and reference reconstruction for tests / host-only decoding, and a stand-alone device
 // reconstruction of a list of uploads (the kernel-vs-reference tests; the serving path runs the same kernels
 // inside Executor::submit) — and of the split JPEG crop encoder (runtime/jpeg_encode.h, kernels/jpeg_fdct.hip): the
-// host encoder and reference arithmetic, a stand-alone device encode of the crops of one frame, and the
-// CropJpegEncoder the detection service drives.
+// host encoder and reference arithmetic, a stand-alone device encode of the crops of one frame, the device entropy
+// coder (kernels/jpeg_huff.hip) alone and its phases on the host, and the CropJpegEncoder the detection service drives.
 #include <hip/hip_runtime.h>
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "kernels/jpeg_desc.h"
+#include "kernels/jpeg_huff_math.h"
 #include "kernels/launch.h"
 #include "runtime/jpeg_decode.h"
 #include "runtime/jpeg_encode.h"
@@ -114,7 +115,7 @@ constexpr uint8_t kZigzagToNatural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24
 
 // Upload `frame`, encode `boxes` with a CropJpegEncoder of its own, check the guards around its device buffer.
 py::dict encode_device(const U8Array& frame, const py::object& boxes, int device, int64_t capacity_bytes,
-                       bool want_coefs) {
+                       bool want_coefs, const std::string& entropy) {
   check_rgb(frame, "frame");
   const int h = (int)frame.shape(0), w = (int)frame.shape(1);
   std::vector<CropBox> bx = to_boxes(boxes);
@@ -122,7 +123,8 @@ py::dict encode_device(const U8Array& frame, const py::object& boxes, int device
   CropJpegEncoder::Blobs blobs;
   std::vector<std::vector<int16_t>> coefs;
   std::string err;
-  int64_t launches = 0;
+  int64_t launches = 0, d2h_bytes = 0, fallbacks = 0;
+  if (entropy != "host" && entropy != "gpu") throw std::invalid_argument("entropy is 'host' or 'gpu'");
   {
     py::gil_scoped_release nogil;
     check(hipSetDevice(device), "hipSetDevice");
@@ -130,7 +132,7 @@ py::dict encode_device(const U8Array& frame, const py::object& boxes, int device
     check(hipMalloc((void**)&d_frame, bytes), "hipMalloc frame");
     try {
       check(hipMemcpy(d_frame, frame.data(), bytes, hipMemcpyHostToDevice), "H2D frame");
-      CropJpegEncoder enc(device, capacity_bytes, 2);
+      CropJpegEncoder enc(device, capacity_bytes, 2, kCropJpegQuality, entropy);
       enc.keep_coefs = want_coefs;
       std::promise<void> p;
       enc.submit(d_frame, h, w, std::move(bx), [&](CropJpegEncoder::Blobs&& b, std::string&& e) {
@@ -143,6 +145,8 @@ py::dict encode_device(const U8Array& frame, const py::object& boxes, int device
       if (err.empty()) err = enc.check_guards();
       coefs = std::move(enc.last_coefs);
       launches = enc.launches();
+      d2h_bytes = enc.d2h_bytes();
+      fallbacks = enc.entropy_fallbacks();
     } catch (...) {
       (void)hipFree(d_frame);
       throw;
@@ -155,6 +159,8 @@ py::dict encode_device(const U8Array& frame, const py::object& boxes, int device
   for (const auto& b : blobs) bl.append(to_bytes(b));
   out["blobs"] = bl;
   out["launches"] = launches;
+  out["d2h_bytes"] = d2h_bytes;
+  out["entropy_fallbacks"] = fallbacks;
   if (want_coefs) {
     py::list cl;
     for (const auto& c : coefs) {  // device layout: natural order; handed out in zigzag order like the host oracle
@@ -166,6 +172,91 @@ py::dict encode_device(const U8Array& frame, const py::object& boxes, int device
     }
     out["coefs"] = cl;
   }
+  return out;
+}
+
+using I16Array = py::array_t<int16_t, py::array::c_style | py::array::forcecast>;
+
+void check_coefs(int w, int h, const I16Array& coefs, bool domain) {
+  if (w < 1 || h < 1 || w > 65535 || h > 65535) throw std::invalid_argument("bad size");
+  if (coefs.size() != jpeg_enc_blocks(w, h) * 64) throw std::invalid_argument("coefficient count does not match the size");
+  if (!domain) return;
+  const int16_t* p = coefs.data();
+  for (py::ssize_t i = 0; i < coefs.size(); ++i)
+    if (p[i] > jpegh::kMaxCoef || p[i] < -jpegh::kMaxCoef)
+      throw std::invalid_argument("a coefficient lies outside +-1023, the entropy coder's domain");
+}
+
+// The entropy kernels alone over one crop's coefficient blocks, with buffers of their own between guards.
+py::dict entropy_device(int w, int h, const I16Array& coefs, int device, int reserve_per_block, bool natural) {
+  check_coefs(w, h, coefs, true);
+  const int64_t slots = jpeg_enc_blocks(w, h), cbytes = slots * 128;
+  if (slots > 9600) throw std::invalid_argument("more block slots than a 640 x 640 frame slot has");
+  const JpegEncTables t = jpeg_enc_tables(kCropJpegQuality);
+  std::vector<uint8_t> blob;
+  JpegEntResult rec{};
+  int64_t fallbacks = 0;
+  std::string err;
+  {
+    py::gil_scoped_release nogil;
+    constexpr int64_t kGuard = JpegEntropyDevice::kGuard;
+    constexpr int kGuardByte = JpegEntropyDevice::kGuardByte;
+    check(hipSetDevice(device), "hipSetDevice");
+    uint8_t* d_alloc = nullptr;
+    hipStream_t s = nullptr;
+    check(hipMalloc((void**)&d_alloc, (size_t)(cbytes + 2 * kGuard)), "hipMalloc coefficients");
+    try {
+      check(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreate");
+      check(hipMemset(d_alloc, kGuardByte, (size_t)(cbytes + 2 * kGuard)), "hipMemset guards");
+      check(hipMemcpy(d_alloc + kGuard, coefs.data(), (size_t)cbytes, hipMemcpyHostToDevice), "H2D coefficients");
+      JpegEncDesc e{};
+      e.w = w;
+      e.h = h;
+      e.mcux = (w + 15) / 16;
+      e.total_blocks = (int32_t)slots;
+      std::vector<JpegEntDesc> descs;
+      JpegEntropyDevice ent(slots, align256(slots * std::max(reserve_per_block, 1)), 1);
+      err = ent.plan({e}, reserve_per_block, descs);
+      if (err.empty()) err = ent.launch(descs, d_alloc + kGuard, natural, s);
+      if (err.empty()) {
+        check(hipMemcpyAsync(&rec, ent.d_res(), sizeof(rec), hipMemcpyDeviceToHost, s), "D2H record");
+        check(hipStreamSynchronize(s), "jpeg_entropy");
+        if (rec.status == jpegh::kEntropyOk) {
+          if (rec.scan_bytes > (uint32_t)descs[0].reserve) throw std::runtime_error("inconsistent entropy record");
+          blob = jpeg_write_header(w, h, t);
+          const size_t at = blob.size();
+          blob.resize(at + rec.scan_bytes + 2);
+          check(hipMemcpy(blob.data() + at, ent.d_out(), rec.scan_bytes, hipMemcpyDeviceToHost), "D2H scan");
+          blob[at + rec.scan_bytes] = 0xFF;
+          blob[at + rec.scan_bytes + 1] = 0xD9;
+        } else {  // overflow: the coefficients come back and the host codes them
+          std::vector<int16_t> back((size_t)slots * 64);
+          check(hipMemcpy(back.data(), d_alloc + kGuard, (size_t)cbytes, hipMemcpyDeviceToHost), "D2H coefficients");
+          blob = jpeg_write(w, h, back.data(), t, natural);
+          fallbacks = 1;
+        }
+        err = ent.check_guards();
+        uint8_t g[2 * kGuard];
+        check(hipMemcpy(g, d_alloc, (size_t)kGuard, hipMemcpyDeviceToHost), "D2H guards");
+        check(hipMemcpy(g + kGuard, d_alloc + kGuard + cbytes, (size_t)kGuard, hipMemcpyDeviceToHost), "D2H guards");
+        for (int64_t k = 0; k < 2 * kGuard && err.empty(); ++k)
+          if (g[k] != kGuardByte) err = "the entropy kernels wrote outside the coefficient buffer";
+      }
+    } catch (...) {
+      if (s) (void)hipStreamDestroy(s);
+      (void)hipFree(d_alloc);
+      throw;
+    }
+    (void)hipStreamDestroy(s);
+    (void)hipFree(d_alloc);
+  }
+  if (!err.empty()) throw std::runtime_error("jpeg_entropy_device: " + err);
+  py::dict out;
+  out["blob"] = to_bytes(blob);
+  out["status"] = rec.status == jpegh::kEntropyOk ? "ok" : "overflow";
+  out["bits"] = (int64_t)rec.total_bits;
+  out["scan_bytes"] = (int64_t)rec.scan_bytes;
+  out["fallbacks"] = fallbacks;
   return out;
 }
 
@@ -446,30 +537,71 @@ void bind_jpeg(py::module& m) {
 
   m.def(
       "jpeg_encode_device",
-      [](U8Array frame, py::object boxes, int device, int64_t capacity_bytes) -> py::object {
+      [](U8Array frame, py::object boxes, int device, int64_t capacity_bytes, std::string entropy) -> py::object {
         // the dict outlives the lookup: an item accessor of a temporary dict would be read after the dict is gone
-        const py::dict out = encode_device(frame, boxes, device, capacity_bytes, false);
+        const py::dict out = encode_device(frame, boxes, device, capacity_bytes, false, entropy);
         return out["blobs"];
       },
       py::arg("frame"), py::arg("boxes"), py::arg("device") = 0, py::arg("capacity_bytes") = 0,
+      py::arg("entropy") = "host",
       "Upload an HxWx3 uint8 frame and encode the crops of `boxes` (x1, y1, x2, y2 floats, clipped like\n"
       "crop_bounds) on the GPU: list of bytes.  The encoder's device buffer (capacity_bytes, 0 = default) lies\n"
-      "between guard bytes; raises if the kernel touched them.");
+      "between guard bytes; raises if the kernel touched them.  entropy: \"host\" (C++ threads Huffman-code the\n"
+      "coefficients) or \"gpu\" (kernels/jpeg_huff.hip; its buffers lie between guard bytes too).");
   m.def(
       "jpeg_encode_device_coefs",
-      [](U8Array frame, py::object boxes, int device, int64_t capacity_bytes) {
-        return encode_device(frame, boxes, device, capacity_bytes, true);
+      [](U8Array frame, py::object boxes, int device, int64_t capacity_bytes, std::string entropy, bool keep_coefs) {
+        return encode_device(frame, boxes, device, capacity_bytes, keep_coefs, entropy);
       },
       py::arg("frame"), py::arg("boxes"), py::arg("device") = 0, py::arg("capacity_bytes") = 0,
+      py::arg("entropy") = "host", py::arg("keep_coefs") = true,
       "jpeg_encode_device that also returns what the kernel wrote: dict(blobs, coefs = int16[blocks][64] per box in\n"
-      "zigzag order (empty for an empty box), launches).");
+      "zigzag order (empty for an empty box), launches, d2h_bytes = bytes the encoder copied device to host,\n"
+      "entropy_fallbacks = crops whose device-coded scan overflowed its reserve and the host coded).\n"
+      "keep_coefs=False leaves `coefs` out, and with it the copy of the coefficients entropy=\"gpu\" does not need.");
+
+  m.def(
+      "jpeg_write_header",
+      [](int w, int h) {
+        if (w < 1 || h < 1 || w > 65535 || h > 65535) throw std::invalid_argument("bad size");
+        return to_bytes(jpeg_write_header(w, h, jpeg_enc_tables(kCropJpegQuality)));
+      },
+      py::arg("w"), py::arg("h"), "What jpeg_write puts before the scan: SOI up to and including the SOS header.");
+  m.def(
+      "jpeg_block_bits",
+      [](int w, int h, I16Array coefs, bool natural) {
+        check_coefs(w, h, coefs, true);
+        const std::vector<uint32_t> b = jpeg_block_bits_host(w, h, coefs.data(), natural);
+        py::array_t<uint32_t> a((py::ssize_t)b.size());
+        std::memcpy(a.mutable_data(), b.data(), b.size() * sizeof(uint32_t));
+        return a;
+      },
+      py::arg("w"), py::arg("h"), py::arg("coefs"), py::arg("natural") = false,
+      "Size phase of the entropy coder on the host (kernels/jpeg_huff_math.h block_bits): the bits jpeg_write emits\n"
+      "for every block slot, uint32[blocks].");
+  m.def(
+      "jpeg_entropy_phased_host",
+      [](int w, int h, I16Array coefs, bool natural) {
+        check_coefs(w, h, coefs, true);
+        return to_bytes(jpeg_entropy_phased_host(w, h, coefs.data(), jpeg_enc_tables(kCropJpegQuality), natural));
+      },
+      py::arg("w"), py::arg("h"), py::arg("coefs"), py::arg("natural") = false,
+      "jpeg_write's bytes made on the CPU through the device entropy coder's phases (size, scan, emit, stuff) with\n"
+      "the functions of kernels/jpeg_huff_math.h.  Coefficients must lie in +-1023.");
+  m.def("jpeg_entropy_device", &entropy_device, py::arg("w"), py::arg("h"), py::arg("coefs"), py::arg("device") = 0,
+        py::arg("reserve_per_block") = jpegh::kEntropyReserve, py::arg("natural") = false,
+        "Upload one crop's coefficient blocks (jpeg_write's layout) and run only the entropy kernels\n"
+        "(kernels/jpeg_huff.hip): dict(blob = the whole file, status = ok | overflow, bits = scan bits before padding,\n"
+        "scan_bytes, fallbacks).  A scan that does not fit reserve_per_block bytes per block slot is coded by\n"
+        "jpeg_write instead (status overflow, fallbacks 1).  Raises if a guard byte around the kernels' buffers was\n"
+        "touched or a coefficient lies outside +-1023.");
 
   py::class_<CropJpegEncoder>(m, "CropJpegEncoder")
-      .def(py::init([](int device, int64_t capacity_bytes, int threads) {
+      .def(py::init([](int device, int64_t capacity_bytes, int threads, std::string entropy) {
              py::gil_scoped_release nogil;
-             return new CropJpegEncoder(device, capacity_bytes, threads);
+             return new CropJpegEncoder(device, capacity_bytes, threads, kCropJpegQuality, entropy);
            }),
-           py::arg("device") = 0, py::arg("capacity_bytes") = 0, py::arg("threads") = 2)
+           py::arg("device") = 0, py::arg("capacity_bytes") = 0, py::arg("threads") = 2, py::arg("entropy") = "host")
       .def(
           "submit",
           [](CropJpegEncoder& e, uintptr_t frame_ptr, int frame_h, int frame_w, py::object boxes, py::function done,
@@ -504,6 +636,9 @@ void bind_jpeg(py::module& m) {
           "thread; the frame must stay valid until then.")
       .def_property_readonly("capacity", &CropJpegEncoder::capacity)
       .def_property_readonly("launches", &CropJpegEncoder::launches)
+      .def_property_readonly("d2h_bytes", &CropJpegEncoder::d2h_bytes)
+      .def_property_readonly("entropy_fallbacks", &CropJpegEncoder::entropy_fallbacks)
+      .def_property_readonly("entropy", [](const CropJpegEncoder& e) { return e.entropy_gpu() ? "gpu" : "host"; })
       .def("stop", [](CropJpegEncoder& e) {
         py::gil_scoped_release nogil;
         e.stop();

@@ -552,4 +552,25 @@ struct JpegEncDesc;
 void jpeg_forward(const JpegEncDesc* d_descs, const uint8_t* d_frame, uint8_t* d_coef, const uint16_t* d_qt,
                   int n_crops, int max_blocks, hipStream_t s);
 
+// Device entropy coder of the crop encoder (csrc/kernels/jpeg_huff.hip): for n_crops descriptors (jpeg_enc_desc.h)
+// Huffman-code the coefficient blocks at coef + desc.coef_off (the layout jpeg_forward writes; natural = false: each
+// block in zigzag order) and write the byte-stuffed scan at out + desc.out_off and the crop's record at res[crop].
+// A scan longer than desc.reserve is not written (status overflow).  slot_bits: one uint32 per block slot; bitbuf:
+// 256 bytes per block slot, zeroed before every call on the same stream; seg_ff: one uint32 per segment
+// (jpegh::stuff_segments per crop); tables: jpeg_enc_code_tables() on the device.  Five launches on `s`; no
+// workgroup waits for another.  The caller has validated every range (JpegEntropyDevice::plan).
+struct JpegEntDesc;
+struct JpegEntResult;
+struct JpegEntBuffers {
+  const uint8_t* coef;
+  const uint32_t* tables;
+  uint32_t* slot_bits;
+  uint8_t* bitbuf;
+  uint32_t* seg_ff;
+  uint8_t* out;
+  JpegEntResult* res;
+};
+void jpeg_entropy(const JpegEntDesc* d_descs, const JpegEntBuffers& b, int n_crops, int max_blocks, bool natural,
+                  hipStream_t s);
+
 }  // namespace arena

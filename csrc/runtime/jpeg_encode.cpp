@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "../kernels/jpeg_enc_math.h"
+#include "../kernels/jpeg_huff_math.h"
 
 namespace arena {
 
@@ -228,9 +229,8 @@ void jpeg_encode_coefs_host(const uint8_t* rgb, int64_t pitch, int w, int h, con
 template void jpeg_encode_coefs_host<int32_t>(const uint8_t*, int64_t, int, int, const JpegEncTables&, int16_t*, bool);
 template void jpeg_encode_coefs_host<int64_t>(const uint8_t*, int64_t, int, int, const JpegEncTables&, int16_t*, bool);
 
-std::vector<uint8_t> jpeg_write(int w, int h, const int16_t* coefs, const JpegEncTables& t, bool natural) {
+std::vector<uint8_t> jpeg_write_header(int w, int h, const JpegEncTables& t) {
   std::vector<uint8_t> o;
-  const int mcux = (w + 15) / 16, mcuy = (h + 15) / 16;
   o.reserve(1024);
   // SOI, APP0 JFIF 1.01 (no units, density 1x1, no thumbnail)
   const uint8_t head[] = {0xFF, 0xD8, 0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
@@ -261,7 +261,25 @@ std::vector<uint8_t> jpeg_write(int w, int h, const int16_t* coefs, const JpegEn
   }
   const uint8_t sos[] = {0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0};
   o.insert(o.end(), sos, sos + sizeof(sos));
+  return o;
+}
 
+const uint32_t* jpeg_enc_code_tables() {
+  struct Packed {
+    uint32_t e[4 * jpegh::kCodeTableEntries];
+    Packed() {
+      const Codes& cd = codes();
+      for (int k = 0; k < 4; ++k)
+        for (int i = 0; i < 256; ++i) e[k * 256 + i] = (uint32_t)cd.t[k].code[i] | ((uint32_t)cd.t[k].len[i] << 16);
+    }
+  };
+  static const Packed p;
+  return p.e;
+}
+
+std::vector<uint8_t> jpeg_write(int w, int h, const int16_t* coefs, const JpegEncTables& t, bool natural) {
+  std::vector<uint8_t> o = jpeg_write_header(w, h, t);
+  const int mcux = (w + 15) / 16, mcuy = (h + 15) / 16;
   const Codes& cd = codes();
   // real block grid per component: luma ceil(w / 8) x ceil(h / 8), chroma ceil(cw / 8) x ceil(ch / 8)
   const int ybw = (w + 7) / 8, ybh = (h + 7) / 8;
@@ -301,6 +319,110 @@ std::vector<uint8_t> jpeg_write(int w, int h, const int16_t* coefs, const JpegEn
     }
   bw.flush();
   o.insert(o.end(), scan.data(), bw.p);
+  o.push_back(0xFF);
+  o.push_back(0xD9);
+  return o;
+}
+
+namespace {
+
+constexpr bool zigzag_of_inverts_natural() {
+  for (int k = 0; k < 64; ++k)
+    if (jpegh::kZigzagOf[kNatural[k]] != k) return false;
+  return true;
+}
+static_assert(zigzag_of_inverts_natural(), "jpeg_huff_math.h kZigzagOf is the inverse of kNatural");
+
+}  // namespace
+
+std::vector<uint32_t> jpeg_block_bits_host(int w, int h, const int16_t* coefs, bool natural) {
+  const int mcux = (w + 15) / 16, slots = (int)jpeg_enc_blocks(w, h);
+  const uint32_t* tables = jpeg_enc_code_tables();
+  const auto dc_at = [&](int slot) { return (int)coefs[(size_t)slot * 64]; };  // index 0 in either order
+  std::vector<uint32_t> bits((size_t)slots);
+  int16_t zz[64] = {};
+  for (int i = 0; i < slots; ++i) {
+    const int mcu = i / kJpegEncBlocksPerMcu, s = i - mcu * kJpegEncBlocksPerMcu;
+    const bool real = jpegh::slot_real(w, h, mcux, mcu, s);
+    uint64_t nz = 0;
+    if (real) {
+      for (int k = 0; k < 64; ++k) zz[k] = coefs[(size_t)i * 64 + (natural ? kNatural[k] : k)];
+      nz = jpegh::nonzero_mask(zz);
+    }
+    const int diff = jpegh::effective_dc(w, h, mcux, mcu, s, dc_at) - jpegh::predictor(w, h, mcux, mcu, s, dc_at);
+    const uint32_t* tb = jpegh::slot_tables(tables, s);
+    bits[(size_t)i] = (uint32_t)jpegh::block_bits(zz, nz, diff, tb, tb + jpegh::kCodeTableEntries);
+  }
+  return bits;
+}
+
+std::vector<uint8_t> jpeg_entropy_phased_host(int w, int h, const int16_t* coefs, const JpegEncTables& t, bool natural) {
+  const int mcux = (w + 15) / 16, slots = (int)jpeg_enc_blocks(w, h);
+  const uint32_t* tables = jpeg_enc_code_tables();
+  const auto dc_at = [&](int slot) { return (int)coefs[(size_t)slot * 64]; };
+  // size, scan
+  std::vector<uint32_t> off = jpeg_block_bits_host(w, h, coefs, natural);
+  uint32_t total = 0;
+  for (uint32_t& b : off) {
+    const uint32_t n = b;
+    b = total;
+    total += n;
+  }
+  // emit: every slot on its own, into a zeroed buffer
+  const uint32_t nbytes = (total + 7) / 8;
+  std::vector<uint32_t> words((size_t)nbytes / 4 + 2, 0u);
+  const auto or_word = [&](uint32_t i, uint32_t v) { words[i] |= v; };
+  int16_t zz[64] = {};
+  for (int i = slots - 1; i >= 0; --i) {  // any order gives the same buffer
+    const int mcu = i / kJpegEncBlocksPerMcu, s = i - mcu * kJpegEncBlocksPerMcu;
+    const uint32_t* tb = jpegh::slot_tables(tables, s);
+    const uint32_t* act = tb + jpegh::kCodeTableEntries;
+    uint64_t nz = 0, code;
+    int len;
+    if (jpegh::slot_real(w, h, mcux, mcu, s)) {
+      for (int k = 0; k < 64; ++k) zz[k] = coefs[(size_t)i * 64 + (natural ? kNatural[k] : k)];
+      nz = jpegh::nonzero_mask(zz);
+    }
+    uint32_t pos = off[(size_t)i];
+    jpegh::dc_symbol(jpegh::effective_dc(w, h, mcux, mcu, s, dc_at) - jpegh::predictor(w, h, mcux, mcu, s, dc_at), tb,
+                     code, len);
+    jpegh::put_bits(pos, code, len, or_word);
+    pos += (uint32_t)len;
+    for (uint64_t m = nz & ~1ull; m; m &= m - 1) {
+      const int k = __builtin_ctzll(m);
+      jpegh::ac_symbol(nz, k, zz[k], act, code, len);
+      jpegh::put_bits(pos, code, len, or_word);
+      pos += (uint32_t)len;
+    }
+    jpegh::eob_symbol(nz, act, code, len);
+    jpegh::put_bits(pos, code, len, or_word);
+  }
+  {
+    uint64_t code;
+    int len;
+    jpegh::pad_symbol(total, code, len);
+    jpegh::put_bits(total, code, len, or_word);
+  }
+  std::vector<uint8_t> raw((size_t)words.size() * 4);
+  for (size_t i = 0; i < words.size(); ++i) {
+    const uint32_t be = jpegh::store_be32(words[i]);
+    std::memcpy(&raw[i * 4], &be, 4);
+  }
+  // stuff: 0xFF bytes per segment, their prefix sum, then every byte at its own position
+  const uint32_t nseg = (nbytes + jpegh::kStuffSegment - 1) / jpegh::kStuffSegment;
+  std::vector<uint32_t> ff((size_t)nseg + 1, 0u);
+  for (uint32_t i = 0; i < nbytes; ++i) ff[(size_t)i / jpegh::kStuffSegment + 1] += raw[i] == 0xFF;
+  for (uint32_t g = 0; g < nseg; ++g) ff[(size_t)g + 1] += ff[g];
+  std::vector<uint8_t> o = jpeg_write_header(w, h, t);
+  const size_t base = o.size();
+  o.resize(base + nbytes + ff[nseg], 0);
+  for (uint32_t g = 0; g < nseg; ++g) {
+    uint32_t before = ff[g];
+    for (uint32_t i = g * jpegh::kStuffSegment; i < std::min(nbytes, (g + 1) * (uint32_t)jpegh::kStuffSegment); ++i) {
+      o[base + jpegh::stuffed_at(i, before)] = raw[i];  // the stuffed 0x00 after it is already there
+      before += raw[i] == 0xFF;
+    }
+  }
   o.push_back(0xFF);
   o.push_back(0xD9);
   return o;

@@ -15,8 +15,10 @@ three from any client.
 ``GpuCropEncoder`` (``ARENA_CROP_ENCODE=gpu``) makes the ``jpeg`` bytes without
 host pixels: the GPU cuts each crop out of the device-resident frame and does
 everything up to quantisation (csrc/kernels/jpeg_fdct.hip), C++ threads do the
-Huffman pass (csrc/runtime/jpeg_encode.h).  The bytes are those of
-``encode_crop(extract_crop(frame, box), "jpeg")``.
+Huffman pass (csrc/runtime/jpeg_encode.h) — or, with ``entropy="gpu"``
+(``ARENA_CROP_ENTROPY=gpu``), the GPU does that too (csrc/kernels/jpeg_huff.hip)
+and only the JPEG bytes come back.  The bytes are those of
+``encode_crop(extract_crop(frame, box), "jpeg")`` either way.
 """
 from __future__ import annotations
 
@@ -70,12 +72,16 @@ class GpuCropEncoder:
     the call has completed; a cancelled caller therefore keeps waiting (the await is shielded) — see
     ``detection_service`` for how the frame's ring slot is held."""
 
-    def __init__(self, device: int = 0, capacity_bytes: int = 0, threads: int = 2, native_encoder=None):
+    def __init__(self, device: int = 0, capacity_bytes: int = 0, threads: int = 2, native_encoder=None,
+                 entropy: str = "host"):
+        if entropy not in ("host", "gpu"):
+            raise ValueError(f"unknown crop entropy mode '{entropy}' (host | gpu)")
         if native_encoder is None:
             from ..ops import native
 
-            native_encoder = native().CropJpegEncoder(device, capacity_bytes, threads)
+            native_encoder = native().CropJpegEncoder(device, capacity_bytes, threads, entropy)
         self.enc = native_encoder
+        self.entropy = entropy
 
     def submit(self, frame_ptr: int, h: int, w: int, det, frame_bytes: int = 0) -> "asyncio.Future[list[bytes]]":
         """Start the encode; the future completes on the running loop with the blobs or a RuntimeError."""

@@ -17,7 +17,8 @@ classification service cuts the crops on its GPU (server/device_transport.py).
 ``ARENA_CROP_ENCODE=gpu`` keeps the reference's wire contract (jpeg crops, the
 same bytes) without host pixels: the detector leaves the frame in a local
 device ring slot and the split encoder (server/crop_codec.GpuCropEncoder) makes
-the crops' JPEGs from there.
+the crops' JPEGs from there; ``ARENA_CROP_ENTROPY=gpu`` has it Huffman-code them
+on the GPU as well.
 
 Run: ``python -m inference_arena_amd.server.detection_service``.
 """
@@ -106,7 +107,7 @@ def create_app(settings: Settings | None = None, detector: DetectorBackend | Non
             if state.get("encoder") is None:
                 from .crop_codec import GpuCropEncoder
 
-                state["encoder"] = GpuCropEncoder(device=int(settings.ARENA_GPU))
+                state["encoder"] = GpuCropEncoder(device=int(settings.ARENA_GPU), entropy=settings.ARENA_CROP_ENTROPY)
                 own_encoder = True
         log.info("service ready")
         yield

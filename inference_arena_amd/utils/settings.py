@@ -57,6 +57,7 @@ class Settings(BaseModel):
     ARENA_CROP_TRANSPORT: str = "jpeg"  # jpeg (reference) | png | raw | device (IPC frame hand-off)
     ARENA_DEVICE_RING_SLOTS: int = 512  # device transport: frames in flight per detection process
     ARENA_CROP_ENCODE: str = "pil"      # jpeg crops: pil (reference, host) | gpu (split encoder, server/crop_codec.py)
+    ARENA_CROP_ENTROPY: str = "host"    # host | gpu, only with ARENA_CROP_ENCODE=gpu: who Huffman-codes the crops
     # jpeg crops on the classification side: pil (reference, thread-pool decode) | gpu (split decoder: Huffman on C++
     # threads, IDCT + colour inside the classifier batch; GpuClassifierBackend.classify_bytes)
     ARENA_CROP_DECODE: str = "pil"

@@ -57,6 +57,7 @@ SOURCES = [
     "kernels/fc_splitk.hip",
     "kernels/jpeg_idct.hip",
     "kernels/jpeg_fdct.hip",
+    "kernels/jpeg_huff.hip",
     "runtime/executor.cpp",
     "runtime/batcher.cpp",
     "runtime/http_front.cpp",
