@@ -578,45 +578,59 @@ static void launch_x3(const ConvParams& p, hipStream_t s, long M) {
   hipLaunchKernelGGL((conv_x3_lds_kernel<MF, NF, WM, WN>), grid, dim3(256), 0, s, p);
 }
 
-// x3 tile variants (ConvParams.impl = kF32X3 + index)
+// x3 tile variants v (ConvParams.impl = kF32X3 + v): (MF, NF, WM, WN)
+#define X3_VARIANTS(X) \
+  X(0, 2, 2, 2, 2)   /*  64 x  64 */ \
+  X(1, 4, 2, 2, 2)   /* 128 x  64 */ \
+  X(2, 2, 4, 2, 2)   /*  64 x 128 */ \
+  X(3, 4, 4, 2, 2)   /* 128 x 128 */ \
+  X(4, 2, 2, 4, 1)   /* 128 x  32 */ \
+  X(5, 1, 4, 4, 1)   /*  64 x  64 (4 x 1 waves) */ \
+  X(6, 2, 4, 4, 1)   /* 128 x  64 (4 x 1 waves) */ \
+  X(7, 1, 2, 2, 2)   /*  32 x  64 */ \
+  X(8, 2, 3, 4, 1)   /* 128 x  48 */ \
+  X(9, 2, 5, 4, 1)   /* 128 x  80 */ \
+  X(10, 1, 1, 4, 1)  /*  64 x  16 */ \
+  X(11, 2, 1, 4, 1)  /* 128 x  16 */
+static_assert(F32_TABLE_ROWS(X3_VARIANTS) == kF32X3Variants, "X3_VARIANTS rows != the family's count (f32_impl.h)");
+
 static bool launch_x3_variant(const ConvParams& p, hipStream_t s, long M, int v) {
   switch (v) {
-    case 0: launch_x3<2, 2, 2, 2>(p, s, M); return true;  // 64 x 64
-    case 1: launch_x3<4, 2, 2, 2>(p, s, M); return true;  // 128 x 64
-    case 2: launch_x3<2, 4, 2, 2>(p, s, M); return true;  // 64 x 128
-    case 3: launch_x3<4, 4, 2, 2>(p, s, M); return true;  // 128 x 128
-    case 4: launch_x3<2, 2, 4, 1>(p, s, M); return true;  // 128 x 32
-    case 5: launch_x3<1, 4, 4, 1>(p, s, M); return true;  // 64 x 64 (4 x 1 waves)
-    case 6: launch_x3<2, 4, 4, 1>(p, s, M); return true;  // 128 x 64 (4 x 1 waves)
-    case 7: launch_x3<1, 2, 2, 2>(p, s, M); return true;  // 32 x 64
-    case 8: launch_x3<2, 3, 4, 1>(p, s, M); return true;  // 128 x 48
-    case 9: launch_x3<2, 5, 4, 1>(p, s, M); return true;  // 128 x 80
-    case 10: launch_x3<1, 1, 4, 1>(p, s, M); return true; // 64 x 16
-    case 11: launch_x3<2, 1, 4, 1>(p, s, M); return true; // 128 x 16
+#define X3_CASE(V, MF, NF, WM, WN) \
+  case V: launch_x3<MF, NF, WM, WN>(p, s, M); return true;
+    X3_VARIANTS(X3_CASE)
+#undef X3_CASE
     default: return false;
   }
 }
 
-// Explicit tile variants (ConvParams.impl = 10 + index): the sweep table of tools/bench_f32_convs.py.
+// Explicit tile variants v (ConvParams.impl = kF32LdsTile + v): the sweep table of tools/bench_f32_convs.py.
 // (MF, NF, WM, WN, KC): BM = WM*MF*16 pixels x BN = WN*NF*16 channels, KC k per LDS chunk.
+#define LDS_VARIANTS(X) \
+  X(0, 2, 2, 2, 2, 32)   /*  64 x  64 */ \
+  X(1, 4, 2, 2, 2, 32)   /* 128 x  64 */ \
+  X(2, 2, 4, 2, 2, 32)   /*  64 x 128 */ \
+  X(3, 4, 4, 2, 2, 32)   /* 128 x 128 */ \
+  X(4, 2, 2, 2, 2, 64)   /*  64 x  64, K64 */ \
+  X(5, 4, 2, 2, 2, 64)   /* 128 x  64, K64 */ \
+  X(6, 2, 4, 2, 2, 64)   /*  64 x 128, K64 */ \
+  X(7, 2, 2, 4, 1, 32)   /* 128 x  32 */ \
+  X(8, 4, 1, 4, 1, 32)   /* 256 x  16 */ \
+  X(9, 2, 3, 4, 1, 32)   /* 128 x  48 */ \
+  X(10, 2, 5, 4, 1, 32)  /* 128 x  80 */ \
+  X(11, 1, 4, 4, 1, 32)  /*  64 x  64 (4 x 1 waves) */ \
+  X(12, 2, 4, 4, 1, 32)  /* 128 x  64 (4 x 1 waves) */ \
+  X(13, 1, 2, 2, 2, 32)  /*  32 x  64 */ \
+  X(14, 2, 2, 4, 1, 64)  /* 128 x  32, K64 */ \
+  X(15, 2, 3, 4, 1, 64)  /* 128 x  48, K64 */
+static_assert(F32_TABLE_ROWS(LDS_VARIANTS) == kF32LdsTileVariants, "LDS_VARIANTS rows != the family's count (f32_impl.h)");
+
 static bool launch_lds_variant(const ConvParams& p, hipStream_t s, long M, int v) {
   switch (v) {
-    case 0: launch_lds<2, 2, 2, 2, 32>(p, s, M); return true;   // 64 x 64
-    case 1: launch_lds<4, 2, 2, 2, 32>(p, s, M); return true;   // 128 x 64
-    case 2: launch_lds<2, 4, 2, 2, 32>(p, s, M); return true;   // 64 x 128
-    case 3: launch_lds<4, 4, 2, 2, 32>(p, s, M); return true;   // 128 x 128
-    case 4: launch_lds<2, 2, 2, 2, 64>(p, s, M); return true;   // 64 x 64, K64
-    case 5: launch_lds<4, 2, 2, 2, 64>(p, s, M); return true;   // 128 x 64, K64
-    case 6: launch_lds<2, 4, 2, 2, 64>(p, s, M); return true;   // 64 x 128, K64
-    case 7: launch_lds<2, 2, 4, 1, 32>(p, s, M); return true;   // 128 x 32
-    case 8: launch_lds<4, 1, 4, 1, 32>(p, s, M); return true;   // 256 x 16
-    case 9: launch_lds<2, 3, 4, 1, 32>(p, s, M); return true;   // 128 x 48
-    case 10: launch_lds<2, 5, 4, 1, 32>(p, s, M); return true;  // 128 x 80
-    case 11: launch_lds<1, 4, 4, 1, 32>(p, s, M); return true;  // 64 x 64 (4 x 1 waves)
-    case 12: launch_lds<2, 4, 4, 1, 32>(p, s, M); return true;  // 128 x 64 (4 x 1 waves)
-    case 13: launch_lds<1, 2, 2, 2, 32>(p, s, M); return true;  // 32 x 64
-    case 14: launch_lds<2, 2, 4, 1, 64>(p, s, M); return true;  // 128 x 32, K64
-    case 15: launch_lds<2, 3, 4, 1, 64>(p, s, M); return true;  // 128 x 48, K64
+#define LDS_CASE(V, MF, NF, WM, WN, KC) \
+  case V: launch_lds<MF, NF, WM, WN, KC>(p, s, M); return true;
+    LDS_VARIANTS(LDS_CASE)
+#undef LDS_CASE
     default: return false;
   }
 }
@@ -1572,6 +1586,40 @@ static bool x3_stream(const ConvParams& p, hipStream_t s, int nf_force) {
   }
 }
 
+// Variant v of family f on conv p: false, with nothing launched, if the family does not take the conv.  The families
+// whose id fixes a channel tile or a tile height pass it on here.
+static bool f32_family_run(F32Family f, const ConvParams& p, hipStream_t s, int v) {
+  const long M = (long)p.B * p.Ho * p.Wo;
+  switch (f) {
+    case F32Family::LdsTile: return launch_lds_variant(p, s, M, v);
+    case F32Family::Halo: return halo_f32(p, s, true);
+    case F32Family::X3: return launch_x3_variant(p, s, M, v);
+    case F32Family::X3Halo: return x3_halo(p, s, 0, 8);
+    case F32Family::X3HaloN3: return x3_halo(p, s, 3, 8);
+    case F32Family::X3HaloN2: return x3_halo(p, s, 2, 8);
+    case F32Family::Stream: return x3_stream(p, s, 0);
+    case F32Family::StreamN2: return x3_stream(p, s, 2);
+    case F32Family::Fc: return conv_fc_f32(p, s);
+    case F32Family::StreamExact: return f32_stream(p, s);
+    case F32Family::X3Halo16: return x3_halo(p, s, 0, 16);
+    case F32Family::X3Halo16N3: return x3_halo(p, s, 3, 16);
+    case F32Family::X3H16: return x3_h16(p, s);
+    case F32Family::X3G: return conv_x3g(p, s, v);
+    case F32Family::X3HG: return conv_x3hg(p, s, v);
+    case F32Family::X3HGPw: return conv_x3hg_pw(p, s, v);
+    case F32Family::X3HGPwSmall: return conv_x3hg_pw(p, s, kF32X3HGPwVariants + v);
+    case F32Family::X3HR: return conv_x3hr(p, s, v);
+    case F32Family::X3HRPw: return conv_x3hr_pw(p, s, v);
+    case F32Family::X3HP: return conv_x3hp(p, s, v);
+    case F32Family::X3GSK: return conv_x3g_sk(p, s, v);
+    case F32Family::Policy:
+    case F32Family::Direct:
+    case F32Family::Lds:
+    case F32Family::Invalid: break;  // conv2d_f32's own policy code
+  }
+  return false;
+}
+
 void conv2d_f32(const ConvParams& p, hipStream_t s) {
   if (p.Cin % 4 != 0 || p.xs % 4 != 0 || p.Kpad % 16 != 0 || p.Cout_pad % 16 != 0 || p.Cout % 4 != 0 ||
       p.Cout > p.Cout_pad || p.ys % 4 != 0)
@@ -1579,17 +1627,15 @@ void conv2d_f32(const ConvParams& p, hipStream_t s) {
   if (p.Cin < 16) throw std::runtime_error("conv2d_f32: Cin must be >= 16");
   if (p.Kpad < p.KH * p.KW * p.Cin) throw std::runtime_error("conv2d_f32: Kpad < KH*KW*Cin");
   if ((p.n_lo != 0 || p.n_hi != 0 || p.marks != nullptr) &&
-      !(p.pw_w == nullptr && p.impl >= kF32X3HP && p.impl < kF32X3HP + kF32X3HPVariants))
+      !(p.pw_w == nullptr && f32_conv_impl_in(p.impl, F32Family::X3HP)))
     throw std::runtime_error("conv2d_f32: an output-channel window or a mark gate needs an x3hp variant");
   if (p.pw_w != nullptr) {  // fused Detect-head 1x1: only the x3hg epilogue variants implement it
-    if (p.impl >= kF32X3HRPw && p.impl < kF32X3HRPw + kF32X3HRPwVariants) {
-      if (!conv_x3hr_pw(p, s, p.impl - kF32X3HRPw))
-        throw std::runtime_error("conv2d_f32: a fused pointwise epilogue needs an x3hr-pw variant that fits the conv");
+    if (f32_conv_impl_in(p.impl, F32Family::X3HRPw)) {
+      if (!conv_x3hr_pw(p, s, p.impl - kF32X3HRPw)) throw std::runtime_error(f32_family(F32Family::X3HRPw).reject);
       return;
     }
     const int v = x3hg_pw_variant(p.impl, p.Cout_pad);
-    if (v < 0 || !conv_x3hg_pw(p, s, v))
-      throw std::runtime_error("conv2d_f32: a fused pointwise epilogue needs an x3hg-pw variant that fits the conv");
+    if (v < 0 || !conv_x3hg_pw(p, s, v)) throw std::runtime_error(f32_family(F32Family::X3HGPw).reject);
     return;
   }
   if (p.res != nullptr && p.rs % 4 != 0) throw std::runtime_error("conv2d_f32: residual stride % 4");
@@ -1603,70 +1649,15 @@ void conv2d_f32(const ConvParams& p, hipStream_t s) {
       throw std::runtime_error("conv2d_f32: a letterbox-source conv must be a 3x3 s1 pad-1 conv over 16 channels");
     return;
   }
+  const F32Impl fv = f32_conv_impl_find(p.impl);
+  if (fv.family == F32Family::Invalid)
+    throw std::runtime_error("conv2d_f32: impl " + std::to_string(p.impl) + " names no fp32 conv kernel");
   if (p.impl >= 10) {  // explicit variant (autotune table / microbenchmarks)
-    if (p.impl >= kF32X3G && p.impl < kF32X3G + kF32X3GVariants) {
-      if (!conv_x3g(p, s, p.impl - kF32X3G))
-        throw std::runtime_error("conv2d_f32: not an x3g-eligible conv (needs pre-split weights)");
-      return;
-    }
-    if (p.impl >= kF32X3GSK && p.impl < kF32X3GSK + kF32X3GSKVariants) {
-      if (!conv_x3g_sk(p, s, p.impl - kF32X3GSK))
-        throw std::runtime_error("conv2d_f32: not a split-K x3g-eligible conv (pre-split weights, workspace)");
-      return;
-    }
-    if (p.impl >= kF32X3HG && p.impl < kF32X3HG + kF32X3HGVariants) {
-      if (!conv_x3hg(p, s, p.impl - kF32X3HG))
-        throw std::runtime_error("conv2d_f32: not an x3hg-eligible conv (3x3 s1 with pre-split weights)");
-      return;
-    }
-    if (p.impl >= kF32X3HR && p.impl < kF32X3HR + kF32X3HRVariants) {
-      if (!conv_x3hr(p, s, p.impl - kF32X3HR))
-        throw std::runtime_error("conv2d_f32: not an x3hr-eligible conv (3x3 s1 with pre-split weights)");
-      return;
-    }
-    if (p.impl >= kF32X3HP && p.impl < kF32X3HP + kF32X3HPVariants) {
-      if (!conv_x3hp(p, s, p.impl - kF32X3HP))
-        throw std::runtime_error("conv2d_f32: not an x3hp-eligible conv (3x3 s1 with pre-split weights)");
-      return;
-    }
-    if (p.impl == kF32X3H16) {
-      if (!x3_h16(p, s)) throw std::runtime_error("conv2d_f32: not an x3-h16-eligible conv (3x3 s1 over 16 channels)");
-      return;
-    }
-    if (p.impl == kF32Fc) {
-      if (!conv_fc_f32(p, s)) throw std::runtime_error("conv2d_f32: not an FC-eligible conv (1x1 map, Kpad 1280)");
-      return;
-    }
-    if (p.impl == kF32StreamExact) {
-      if (!f32_stream(p, s)) throw std::runtime_error("conv2d_f32: not a stream-eligible conv (Cin % 4, Kpad <= 192)");
-      return;
-    }
-    if (p.impl == kF32Stream || p.impl == kF32StreamN2) {
-      if (!x3_stream(p, s, p.impl == kF32StreamN2 ? 2 : 0))
-        throw std::runtime_error("conv2d_f32: not a stream-eligible conv (Cin % 8, Kpad <= 192)");
-      return;
-    }
-    if (p.impl == kF32X3Halo || p.impl == kF32X3HaloN3 || p.impl == kF32X3HaloN2 || p.impl == kF32X3Halo16 ||
-        p.impl == kF32X3Halo16N3) {
-      const int nf = (p.impl == kF32X3HaloN3 || p.impl == kF32X3Halo16N3) ? 3 : p.impl == kF32X3HaloN2 ? 2 : 0;
-      const int th = (p.impl == kF32X3Halo16 || p.impl == kF32X3Halo16N3) ? 16 : 8;
-      if (!x3_halo(p, s, nf, th)) throw std::runtime_error("conv2d_f32: not an x3-halo-eligible conv");
-      return;
-    }
-    if (p.impl == kF32Halo) {
-      if (!halo_f32(p, s, true)) throw std::runtime_error("conv2d_f32: not a halo-eligible conv");
-      return;
-    }
-    if (p.impl >= kF32X3) {
-      if (p.impl >= kF32X3 + kF32X3Variants || !launch_x3_variant(p, s, M, p.impl - kF32X3))
-        throw std::runtime_error("conv2d_f32: unknown x3 variant");
-      return;
-    }
-    if (p.impl >= 10 + kF32Variants || !launch_lds_variant(p, s, M, p.impl - 10)) throw std::runtime_error("conv2d_f32: unknown variant");
+    if (!f32_family_run(fv.family, p, s, fv.v)) throw std::runtime_error(f32_family(fv.family).reject);
     return;
   }
   if (p.impl == 0 && conv_fc_f32(p, s)) return;  // classifier FC: split-K over the 1x1 map
-  const int impl = p.impl == 1 ? 1 : p.impl >= 2 ? 2 : f32_conv_family();
+  const int impl = p.impl != 0 ? p.impl : f32_conv_family();
   if (impl == 2 && halo_f32(p, s)) return;
   if (impl == 2) {
     // channel tile per workgroup (BN = WN*NF*16) by output-channel count

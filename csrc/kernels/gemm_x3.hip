@@ -438,6 +438,10 @@ bool xg_launch_sk(const ConvParams& p, hipStream_t s, int splits) {
   X(8, 4, 2, 2, 1)     /* 256 px x  64 ch, 8 waves */ \
   X(9, 4, 2, 1, 1)     /* 128 px x  64 ch, 8 waves */
 
+// every XG_VARIANTS row is two variants: v, and v + 10 with the interleaved schedule
+static_assert(2 * F32_TABLE_ROWS(XG_VARIANTS) == kF32X3GVariants, "XG_VARIANTS rows != the family's count (f32_impl.h)");
+static_assert(F32_TABLE_ROWS(XG_SK_VARIANTS) == kF32X3GSKVariants,
+              "XG_SK_VARIANTS rows != the family's count (f32_impl.h)");
 
 }  // namespace
 

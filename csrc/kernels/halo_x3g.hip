@@ -631,6 +631,13 @@ void hr_launch(const ConvParams& p, hipStream_t s) {
   X(4, 8, 4, 1, 2, 2)   \
   X(5, 8, 4, 1, 3, 3)
 
+static_assert(F32_TABLE_ROWS(HG_VARIANTS) == kF32X3HGVariants, "HG_VARIANTS rows != the family's count (f32_impl.h)");
+static_assert(F32_TABLE_ROWS(HG_PW_VARIANTS) == kF32X3HGPwVariants + kF32X3HGPwSmallVariants,
+              "HG_PW_VARIANTS rows != the two families' counts (f32_impl.h)");
+static_assert(F32_TABLE_ROWS(HR_VARIANTS) == kF32X3HRVariants, "HR_VARIANTS rows != the family's count (f32_impl.h)");
+static_assert(F32_TABLE_ROWS(HR_PW_VARIANTS) == kF32X3HRPwVariants,
+              "HR_PW_VARIANTS rows != the family's count (f32_impl.h)");
+
 }  // namespace
 
 bool x3hg_supported(const ConvParams& p) {
@@ -653,11 +660,10 @@ bool x3hg_pw_supported(const ConvParams& p, int bn, int pwn) {
 }
 
 int x3hg_pw_variant(int impl, int cout_pad) {
-  return impl >= kF32X3HGPw && impl < kF32X3HGPw + kF32X3HGPwVariants ? impl - kF32X3HGPw
-         : impl >= kF32X3HGPwSmall && impl < kF32X3HGPwSmall + kF32X3HGPwSmallVariants
-             ? kF32X3HGPwVariants + impl - kF32X3HGPwSmall
-         : impl == 0 ? (cout_pad <= 64 ? 0 : 2)
-                     : -1;
+  return f32_conv_impl_in(impl, F32Family::X3HGPw)        ? impl - kF32X3HGPw
+         : f32_conv_impl_in(impl, F32Family::X3HGPwSmall) ? kF32X3HGPwVariants + impl - kF32X3HGPwSmall
+         : impl == 0                                      ? (cout_pad <= 64 ? 0 : 2)
+                                                          : -1;
 }
 
 bool x3hg_pw_tile(int impl, int cout_pad, int* th, int* tw) {

@@ -288,6 +288,8 @@ void hp_launch(const ConvParams& p0, hipStream_t s) {
   X(8, 9, 16, 1)  /* 16 x 16 px x 144 ch, 8 waves */ \
   X(9, 5, 8, 1)   /*  8 x 16 px x  80 ch, per-tap stages: the class window of a split Detect-head conv */
 
+static_assert(F32_TABLE_ROWS(HP_VARIANTS) == kF32X3HPVariants, "HP_VARIANTS rows != the family's count (f32_impl.h)");
+
 }  // namespace
 
 bool x3hp_supported(const ConvParams& p) {

@@ -10,6 +10,8 @@
 #include <stdexcept>
 #include <string>
 
+#include "f32_impl.h"
+
 namespace arena {
 
 // ---------------------------------------------------------------- conv (K2/K3/K4/K6/K10/K11/K13)
@@ -92,59 +94,20 @@ int get_conv_impl();
 // Exact-fp32 pipeline (csrc/kernels/conv_f32.hip): the same ConvParams geometry and epilogue with fp32
 // activations, fp32 weights [Cout_pad][Kpad] (Kpad a multiple of 16) and v_mfma_f32_16x16x4_f32 (one
 // rounding per product, fp32 accumulation: the reference's ONNX Runtime fp32 numerics).
-// fp32 conv ConvParams.impl values beyond the families 0 (policy) / 1 (direct) / 2 (LDS): 10 + v selects LDS
-// implicit-GEMM tile variant v < kF32Variants (conv_f32.hip launch_lds_variant), kF32Halo the 3x3 halo kernel.
-// kF32X3 + v the fp32-accurate triple-bf16-split implicit GEMM variant v < kF32X3Variants (launch_x3_variant).
-constexpr int kF32Variants = 16;
-constexpr int kF32X3 = 40;
-constexpr int kF32X3Variants = 12;
-constexpr int kF32Halo = 100;
-constexpr int kF32X3Halo = 101;  // 3x3 stride-1 halo tiles with the triple-bf16 split
-constexpr int kF32X3HaloN3 = 102;  // ... with 48-channel tiles
-constexpr int kF32X3HaloN2 = 103;  // ... with 32-channel tiles
-constexpr int kF32Stream = 104;    // weight-stationary streaming conv, triple-bf16 split (Cin % 8, Kpad <= 192)
-constexpr int kF32StreamN2 = 105;  // ... with 32-channel tiles
-constexpr int kF32Fc = 106;        // split-K FC over a 1x1 map (fc_splitk.hip), exact fp32
-constexpr int kF32StreamExact = 107;  // streaming small-K conv on exact fp32 MFMA (no split)
-constexpr int kF32X3Halo16 = 108;    // x3 halo tiles of 16 x 16 output pixels (8 waves)
-constexpr int kF32X3Halo16N3 = 109;  // ... with 48-channel tiles
-constexpr int kF32X3H16 = 110;       // x3 3x3 stride-1 conv over exactly 16 input channels (s2d stems)
-constexpr int kF32X3G = 111;         // x3g: 32x32x16 MFMA implicit GEMM over pre-split weights, variant v
-constexpr int kF32X3GVariants = 20;  // v >= 10: v - 10 with the interleaved schedule   // impl kF32X3G + v, v < kF32X3GVariants (gemm_x3.hip XG_VARIANTS)
+// ConvParams.impl of an fp32 conv names a kernel family and a variant of it: f32_impl.h holds the table, the kF32*
+// constants and the lookups.
 void x3_halo_prepare();
 bool x3g_supported(const ConvParams& p);
-bool conv_x3g(const ConvParams& p, hipStream_t s, int v);  // false if the conv or variant is not supported
-// split-K x3g for small grids (bucket-1 latency): variant v = tile x splits (gemm_x3.hip XG_SK_VARIANTS); false when
-// the workspace is missing or too small
-constexpr int kF32X3GSK = 171;
-constexpr int kF32X3GSKVariants = 9;
-bool conv_x3g_sk(const ConvParams& p, hipStream_t s, int v);
+// the launchers below: false, with nothing launched, if the conv or variant v of the family is not supported
+bool conv_x3g(const ConvParams& p, hipStream_t s, int v);
+bool conv_x3g_sk(const ConvParams& p, hipStream_t s, int v);  // runs the tile unsplit where sk_ws cannot hold the conv
 void x3g_prepare();
-// x3hg: 3x3 stride-1 halo tiles on 32x32x16 MFMAs over the same pre-split weights (halo_x3g.hip), variant v
-constexpr int kF32X3HG = 131;
-constexpr int kF32X3HGVariants = 14;
 bool x3hg_supported(const ConvParams& p);
-bool conv_x3hg(const ConvParams& p, hipStream_t s, int v);  // false if the conv or variant is not supported
+bool conv_x3hg(const ConvParams& p, hipStream_t s, int v);
 void x3hg_prepare();
-// ... with the Detect head's final 1x1 fused into the epilogue (ConvParams.pw_*, fp32), variant v
-constexpr int kF32X3HGPw = 145;
-constexpr int kF32X3HGPwVariants = 6;
-// ... two more fused-1x1 tiles of 8 x 8 pixels on 2 waves (more workgroups for bucket 1 / 2): variants 6, 7
-constexpr int kF32X3HGPwSmall = 181;
-constexpr int kF32X3HGPwSmallVariants = 2;
-bool conv_x3hg_pw(const ConvParams& p, hipStream_t s, int v);
-// x3hr: the x3hg tiles with per-wave register weights (no weight LDS stage, two barriers per 16-channel chunk),
-// variant v; and with the fused Detect-head 1x1
-constexpr int kF32X3HR = 151;
-constexpr int kF32X3HRVariants = 10;
-constexpr int kF32X3HRPw = 161;
-constexpr int kF32X3HRPwVariants = 6;
-// x3hp: the 16x16x32 halo tiles of kF32X3Halo* over the pre-split weights (halo_x3p.hip), variant v; bit-identical
-// to impl 101 / 102 / 103 / 108 / 109 on every conv they take
-constexpr int kF32X3HP = 191;
-constexpr int kF32X3HPVariants = 10;
+bool conv_x3hg_pw(const ConvParams& p, hipStream_t s, int v);  // v: row of HG_PW_VARIANTS (x3hg_pw_variant)
 bool x3hp_supported(const ConvParams& p);
-bool conv_x3hp(const ConvParams& p, hipStream_t s, int v);  // false if the conv or variant is not supported
+bool conv_x3hp(const ConvParams& p, hipStream_t s, int v);
 void x3hp_prepare();
 // fused-1x1 x3hg variant (halo_x3g.hip HG_PW_VARIANTS) that conv2d_f32 runs for ConvParams.impl on a conv with
 // cout_pad padded output channels (kF32X3HGPw + v, kF32X3HGPwSmall + v, 0 = by channel count), -1: none; and its
@@ -244,11 +207,11 @@ bool ir_s2k16_x3(const IrParams& p, hipStream_t s);
 void set_ir_s2k16(bool v);  // ARENA_IR_S2K16=0: that block stays on ir_f32.hip's exact-fp32 MFMAs
 void ir_prepare();
 void set_ir_t14(bool v);  // ARENA_IR_T14=1: stride-1 14x14 blocks use one whole-crop tile
-void set_ir_crop(bool v);
-void set_ir_crop_split(int v);  // ARENA_IR_CROP_SPLIT: workgroups per crop in ir_crop (1 or 2)  // ARENA_IR_CROP=0: 7x7-output blocks use the tile kernel (ir_crop.hip)
-void set_ir_wave(bool v);
+void set_ir_crop(bool v);  // ARENA_IR_CROP=0: 7x7-output blocks use the tile kernel (ir_crop.hip)
+void set_ir_crop_split(int v);  // ARENA_IR_CROP_SPLIT: workgroups per crop in ir_crop (1 or 2)
+void set_ir_wave(bool v);  // ARENA_IR_WAVE=0: stride-1 blocks use the block-cooperative kernel
 void set_irx_slices_big(int n);  // hidden slices at most for crop capacities > 32 (< 1: ARENA_IRX_SLICES_BIG, default 2)
-void set_irx_parts(int n);  // row bands per crop of the 14x14 whole-map fp32 IR kernel (2, 3, 4; else auto)  // ARENA_IR_WAVE=0: stride-1 blocks use the block-cooperative kernel
+void set_irx_parts(int n);  // row bands per crop of the 14x14 whole-map fp32 IR kernel (2, 3, 4; else auto)
 
 // ---------------------------------------------------------------- fused C3 block (K2/K3/K4 at 160x160 / 80x80)
 // cv1|cv2 (1x1) -> NB x Bottleneck(1x1, 3x3 [+res]) -> cv3 (1x1) with every intermediate in LDS

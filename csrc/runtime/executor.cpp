@@ -361,19 +361,7 @@ void Executor::add_bucket(int B, const int64_t* offsets, int n_buffers, int64_t 
     for (size_t i = 0; i < prog_.size(); ++i) {
       const int v = (*impl)[i];
       const bool f32 = prog_[i][kDtypeField] == 1;
-      const bool ok = f32 ? (v >= 0 && v <= 2) || (v >= 10 && v < 10 + kF32Variants) ||
-                                (v >= kF32X3 && v < kF32X3 + kF32X3Variants) || v == kF32Halo || v == kF32X3Halo ||
-                                v == kF32X3HaloN3 || v == kF32X3HaloN2 || v == kF32Stream || v == kF32StreamN2 ||
-                                v == kF32Fc || v == kF32StreamExact || v == kF32X3Halo16 || v == kF32X3Halo16N3 ||
-                                v == kF32X3H16 || (v >= kF32X3G && v < kF32X3G + kF32X3GVariants) ||
-                                (v >= kF32X3HG && v < kF32X3HG + kF32X3HGVariants) ||
-                                (v >= kF32X3HGPw && v < kF32X3HGPw + kF32X3HGPwVariants) ||
-                                (v >= kF32X3HGPwSmall && v < kF32X3HGPwSmall + kF32X3HGPwSmallVariants) ||
-                                (v >= kF32X3HR && v < kF32X3HR + kF32X3HRVariants) ||
-                                (v >= kF32X3HRPw && v < kF32X3HRPw + kF32X3HRPwVariants) ||
-                                (v >= kF32X3HP && v < kF32X3HP + kF32X3HPVariants) ||
-                                (v >= kF32X3GSK && v < kF32X3GSK + kF32X3GSKVariants)
-                          : v >= 0 && v <= 3;
+      const bool ok = f32 ? f32_conv_impl_valid(v) : v >= 0 && v <= 3;
       if (!ok || (v != 0 && prog_[i][0] != OP_CONV)) throw std::runtime_error("add_bucket: bad tuning entry");
       bk.impl[i] = (int16_t)v;
     }
@@ -395,11 +383,10 @@ void Executor::add_bucket(int B, const int64_t* offsets, int n_buffers, int64_t 
 // Per-bucket conv kernel selection: every conv op of the program is timed
 // eagerly (bucket capacity, full live counts) with each kernel family — bf16:
 // 1 direct MFMA, 2 tiled/LDS (pointwise fast path, 3x3 halo tiles, weight-
-// stationary), 3 LDS-pipelined implicit GEMM; fp32: the default policy (0),
-// the exact-fp32 LDS implicit-GEMM tile variants that won somewhere in the
-// standalone sweep (profiles/r2_fp32_variants.md, impl 10 + v), the 3x3 halo
-// kernel (impl 100) and the fp32-accurate triple-bf16-split kernels (impl
-// 40 + v, 101) — and the fastest is recorded for the graph capture.  Costs
+// stationary), 3 LDS-pipelined implicit GEMM; fp32: kF32Candidates, the
+// default policy (0) and the variants that the family table marks as tried
+// (kernels/f32_impl.h), in the table's order; a family that does not take
+// the conv throws — and the fastest is recorded for the graph capture.  Costs
 // ~100-300 ms per bucket; ARENA_AUTOTUNE=0 disables.  Production starts load
 // the persisted table instead (engine/tuning.py), so the choice is fixed.
 void Executor::autotune(Bucket& bk) {
@@ -412,33 +399,6 @@ void Executor::autotune(Bucket& bk) {
   hipEvent_t e0, e1;
   ARENA_HIP_CHECK(hipEventCreate(&e0));
   ARENA_HIP_CHECK(hipEventCreate(&e1));
-  static const int kF32Candidates[] = {0,      12,     13,     14,     17,     19,     20,         21,
-                                       23,     24,     kF32Halo, kF32X3, kF32X3 + 1, kF32X3 + 4, kF32X3 + 5,
-                                       kF32X3 + 6, kF32X3 + 7, kF32X3 + 8, kF32X3Halo, kF32X3HaloN3,
-                                       kF32X3HaloN2, kF32Stream, kF32StreamN2, kF32Fc, kF32StreamExact,
-                                       kF32X3Halo16, kF32X3Halo16N3, kF32X3H16,
-                                       // x3g variants that won a layer in tools/bench_x3g.py (impl 111 + v)
-                                       kF32X3G + 5, kF32X3G + 6, kF32X3G + 7, kF32X3G + 9, kF32X3G + 15,
-                                       kF32X3G + 16, kF32X3G + 17, kF32X3G + 19,
-                                       // x3hg 3x3 stride-1 halo tiles that won a layer in tools/bench_x3g.py
-                                       // (halo_x3g.hip; they throw on other convs)
-                                       kF32X3HG + 0, kF32X3HG + 1, kF32X3HG + 2, kF32X3HG + 4, kF32X3HG + 6,
-                                       kF32X3HG + 7, kF32X3HG + 8, kF32X3HG + 9, kF32X3HG + 10,
-                                       // ... with the fused Detect-head 1x1 (the only kernels that take those ops)
-                                       kF32X3HGPw + 0, kF32X3HGPw + 1, kF32X3HGPw + 2, kF32X3HGPw + 3,
-                                       kF32X3HGPw + 4, kF32X3HGPw + 5, kF32X3HGPwSmall + 0, kF32X3HGPwSmall + 1,
-                                       // x3hr: the same tiles with per-wave register weights (halo_x3g.hip)
-                                       kF32X3HR + 0, kF32X3HR + 1, kF32X3HR + 2, kF32X3HR + 3, kF32X3HR + 4,
-                                       kF32X3HR + 5, kF32X3HR + 6, kF32X3HR + 7, kF32X3HR + 8, kF32X3HR + 9,
-                                       kF32X3HRPw + 0, kF32X3HRPw + 1, kF32X3HRPw + 2, kF32X3HRPw + 3,
-                                       kF32X3HRPw + 4, kF32X3HRPw + 5,
-                                       // x3hp: the 16-wide halo tiles over pre-split weights (halo_x3p.hip)
-                                       kF32X3HP + 0, kF32X3HP + 1, kF32X3HP + 2, kF32X3HP + 3, kF32X3HP + 4,
-                                       kF32X3HP + 5, kF32X3HP + 6, kF32X3HP + 7, kF32X3HP + 8,
-                                       // split-K x3g (small grids: bucket 1 / 2); skipped where the workspace
-                                       // is too small
-                                       kF32X3GSK + 0, kF32X3GSK + 1, kF32X3GSK + 2, kF32X3GSK + 3, kF32X3GSK + 4,
-                                       kF32X3GSK + 5, kF32X3GSK + 6, kF32X3GSK + 7, kF32X3GSK + 8};
   static const int kBf16Candidates[] = {1, 2, 3};
   for (size_t i = 0; i < prog_.size(); ++i) {
     if (prog_[i][0] != OP_CONV) continue;
@@ -455,8 +415,8 @@ void Executor::autotune(Bucket& bk) {
     std::vector<OpRecord> one(1, prog_[i]);
     float best = 1e30f;
     int best_impl = -1;
-    const int* cand = f32 ? kF32Candidates : kBf16Candidates;
-    const int n_cand = f32 ? (int)(sizeof(kF32Candidates) / sizeof(int)) : 3;
+    const int* cand = f32 ? kF32Candidates.data() : kBf16Candidates;
+    const int n_cand = f32 ? (int)kF32Candidates.size() : 3;
     for (int ci = 0; ci < n_cand; ++ci) {
       const int impl = cand[ci];
       // warm-up (instruction cache, L2); impl 0 reads bk.impl[i], still 0 here = the default policy.
@@ -614,8 +574,8 @@ std::vector<size_t> Executor::exec_plan(const std::vector<OpRecord>& prog, const
     if (!head_gate_min(gp.conf_thr, &gm)) continue;  // a threshold outside the gate's range
     if (prog[li] != prog_[gp.box] || prog[li + 1] != prog_[gp.cls]) continue;  // not that slice of prog_
     const int impl = gp.box < (int)bk.impl.size() ? bk.impl[gp.box] : 0;
-    const bool x3hg_pw = impl == 0 || (impl >= kF32X3HGPw && impl < kF32X3HGPw + kF32X3HGPwVariants) ||
-                         (impl >= kF32X3HGPwSmall && impl < kF32X3HGPwSmall + kF32X3HGPwSmallVariants);
+    const bool x3hg_pw = impl == 0 || f32_conv_impl_in(impl, F32Family::X3HGPw) ||
+                         f32_conv_impl_in(impl, F32Family::X3HGPwSmall);
     if (!x3hg_pw) continue;
     order[li] = (size_t)li + 1;
     order[li + 1] = (size_t)li;
@@ -647,7 +607,7 @@ std::vector<Executor::Step> Executor::launch_plan(const std::vector<OpRecord>& p
     if (k >= steps.size() || k < 2 || steps[k - 2].pos != (size_t)lf || steps[k - 2].kind != LAUNCH_OP) continue;
     if (prog[lf] != prog_[fi] || prog_[fi][30] != BATCH_IMAGES) continue;
     const int f_impl = fi < (int)bk.impl.size() ? bk.impl[fi] : 0;
-    if (!(f_impl >= kF32X3HP && f_impl < kF32X3HP + kF32X3HPVariants)) continue;
+    if (!f32_conv_impl_in(f_impl, F32Family::X3HP)) continue;
     int uh = 0, uw = 0;
     if (gp.box >= (int)bk.impl.size() || !x3hg_pw_tile(bk.impl[gp.box], (int)prog_[gp.box][16], &uh, &uw)) continue;
     if (uh % kMarkCell != 0 || uw % kMarkCell != 0) continue;

@@ -67,7 +67,7 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, stride: in
     ``impl`` pins a kernel (0 = the dispatch policy; fp32: 1 direct, 2 LDS, 10 + v LDS tile variant v,
     40 + v triple-bf16-split variant v, 100 halo, 101 split halo, 102 / 103 split halo with 48 / 32-channel
     tiles, 104 / 105 weight-stationary streaming 1x1 (auto / 32-channel tiles), 111 + v the x3g 32x32x16 GEMM
-    over pre-split weights, 191 + v the 16-wide split halo tiles over pre-split weights — csrc/kernels/launch.h).
+    over pre-split weights, 191 + v the 16-wide split halo tiles over pre-split weights — the whole table: csrc/kernels/f32_impl.h).
     """
     f32 = x.dtype == torch.float32
     B, H, W, Cx = x.shape

@@ -82,8 +82,51 @@ def test_conv_f32_matches_fp64(device, B, H, Cin, Cout, k, s, act, res, up):
         assert torch.equal(out2, up_ref)
 
 
+EXACT_IMPLS = [1, 2] + [10 + v for v in range(16)] + [100]  # direct, LDS, the LDS tile variants, the 3x3 halo kernel
+
+
+@pytest.mark.parametrize(
+    "B,H,Cin,Cout,k,s,act,res",
+    [
+        (3, 20, 32, 32, 3, 1, "silu", True),     # bottleneck 3x3 with residual: every exact-fp32 family takes it
+        (2, 10, 64, 128, 1, 1, "silu", False),   # 1x1: the halo kernel (100) must refuse it
+    ],
+)
+def test_conv_exact_fp32_impls_by_number(device, B, H, Cin, Cout, k, s, act, res):
+    """The exact-fp32 families that the shipped tuning table names and no other test addresses by number (impl 1, 2,
+    10..25, 100) reach a kernel at the fp32 bound; the first numbers past the LDS and x3 tile families (26, 52) name
+    no kernel."""
+    g = torch.Generator().manual_seed(B * 100 + H + Cin + Cout)
+    x32 = torch.randn(B, Cin, H, H, generator=g, dtype=torch.float64).float()
+    w32 = (torch.randn(Cout, Cin, k, k, generator=g, dtype=torch.float64) / (Cin * k * k) ** 0.5).float()
+    b32 = (torch.randn(Cout, generator=g, dtype=torch.float64) * 0.1).float()
+    ref = _act64(F.conv2d(x32.double(), w32.double(), b32.double(), stride=s, padding=k // 2), act)
+    scale = F.conv2d(x32.double().abs(), w32.double().abs(), b32.double().abs(), stride=s, padding=k // 2)
+    r = torch.randn(*ref.shape, generator=g).float() if res else None
+    if res:
+        ref = ref + r.double()
+        scale = scale + r.double().abs()
+    xd = _nhwc(x32).to(device)
+    rd = _nhwc(r).to(device) if res else None
+    packed = AF.pack_weights(w32, b32, device, "fp32")
+    for impl in EXACT_IMPLS:
+        if impl == 100 and k != 3:
+            with pytest.raises(RuntimeError, match="eligible"):
+                AF.conv2d_nhwc(xd, w32, b32, stride=s, act=act, res=rd, packed=packed, impl=impl)
+            continue
+        y = AF.conv2d_nhwc(xd, w32, b32, stride=s, act=act, res=rd, packed=packed, impl=impl)
+        torch.cuda.synchronize()
+        try:
+            _fp32_check(y.permute(0, 3, 1, 2), ref, scale)
+        except AssertionError as e:
+            raise AssertionError(f"impl {impl}: {e}") from None
+    for impl in (26, 52):
+        with pytest.raises(RuntimeError):
+            AF.conv2d_nhwc(xd, w32, b32, stride=s, act=act, res=rd, packed=packed, impl=impl)
+
+
 # x3 tile variants, split halo (auto/48/32), split stream (auto/32), FC, exact-fp32 stream — same fp32 bound
-X3_IMPLS = [40 + v for v in range(12)] + [101, 102, 103, 104, 105, 106, 107, 108, 109, 110] + \
+X3_IMPLS =[40 + v for v in range(12)] + [101, 102, 103, 104, 105, 106, 107, 108, 109, 110] + \
     [111 + v for v in range(20)]
 X3G_IMPLS = [111 + v for v in range(20)]  # x3g: 32x32x16 MFMA GEMM over pre-split weights (gemm_x3.hip)
 X3G_IMPLS += [171 + v for v in range(9)]  # ... split-K (partials in a workspace, summed in split order)
