@@ -1443,6 +1443,7 @@ PYBIND11_MODULE(_C, m) {
              d["native_decoded"] = s.native_decoded;
              d["fallback_decoded"] = s.fallback_decoded;
              d["oriented_decoded"] = s.oriented_decoded;
+             d["layout_decoded"] = s.layout_decoded;
              d["progressive_decoded"] = s.progressive_decoded;
              d["bodies_recycled"] = s.bodies_recycled;
              d["bodies_allocated"] = s.bodies_allocated;

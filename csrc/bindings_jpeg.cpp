@@ -38,6 +38,10 @@ py::dict info_dict(const JpegInfo& in) {
   d["height"] = in.height;
   d["ncomp"] = in.ncomp;
   d["layout"] = in.layout;
+  d["rh"] = in.rh;
+  d["rv"] = in.rv;
+  d["rgb_coded"] = in.rgb_coded;
+  d["multiscan"] = in.multiscan;
   d["orientation"] = in.orientation;
   d["out_width"] = in.out_width;
   d["out_height"] = in.out_height;
@@ -308,7 +312,9 @@ void bind_jpeg(py::module& m) {
         return out;
       },
       py::arg("data"), py::arg("max_pixels") = 0, py::arg("progressive") = py::none(), py::arg("compact") = false,
-      "Host entropy decode: dict(status, error, geometry, comps, coef=int16 natural-order blocks).  progressive:\n"
+      "Host entropy decode: dict(status, error, geometry, comps, coef=int16 natural-order blocks).  layout: 0 grey,\n"
+      "1 4:4:4, 2 4:2:2, 3 4:2:0, 4 4:4:0 (h1v2 fancy), 5 box (each chroma sample over rh x rv pixels); rgb_coded:\n"
+      "no YCbCr step; multiscan: a sequential file whose scans are walked.  progressive:\n"
       "accept SOF2 files (None = the process default, ARENA_JPEG_PROGRESSIVE).  compact=True decodes into the\n"
       "compact payload and expands it (adds compact_bytes).");
 
@@ -347,7 +353,7 @@ void bind_jpeg(py::module& m) {
         std::vector<std::vector<uint8_t>> payload(n);  // compact=True: what the serving paths ship
         std::vector<JpegDesc> descs(n);
         int64_t off = 0, max_blocks = 0, max_pix = 0;
-        bool oriented = false;
+        bool oriented = false, general = false;
         // guard: kGuard bytes of kGuardByte right before and right after every RGB region (not rounded up to the
         // pool's alignment, so one byte past the frame already lands in them), checked after the kernels
         constexpr int64_t kGuard = 256;
@@ -374,6 +380,7 @@ void bind_jpeg(py::module& m) {
           rgb_off[i] = off;
           off = align256(off + (int64_t)in.width * in.height * 3 + (guard ? kGuard : 0));
           oriented |= in.orientation > 1;
+          general |= in.orientation > 1 || jpeg_needs_general(in.layout, in.rgb_coded);
           coef_base[i] = off;
           off = align256(off + jpeg_payload_bytes(in));
           descs[i] = jpeg_device_desc(in, coef_base[i], off, rgb_off[i]);
@@ -406,7 +413,7 @@ void bind_jpeg(py::module& m) {
             if (oriented) throw std::invalid_argument("jpeg_decode_device: ragged=True takes no EXIF-oriented upload");
             jpeg_reconstruct_ragged(dd, pool, n, rplan.idct_units, rplan.color_units, nullptr);
           } else {
-            jpeg_reconstruct(dd, pool, n, (int)max_blocks, max_pix, nullptr, oriented);
+            jpeg_reconstruct(dd, pool, n, (int)max_blocks, max_pix, nullptr, general);
           }
           check(hipGetLastError(), "jpeg_reconstruct launch");
           check(hipDeviceSynchronize(), "jpeg_reconstruct");

@@ -9,8 +9,16 @@ namespace arena {
 
 constexpr int kJpegMaxComp = 3;
 
-// Chroma layouts the split decoder reconstructs on the device; anything else goes to the PIL fallback.
-enum JpegLayout : int32_t { JPEG_GRAY = 0, JPEG_444 = 1, JPEG_422 = 2, JPEG_420 = 3 };
+// Chroma layouts the split decoder reconstructs on the device; anything else goes to the PIL fallback.  The ratio
+// luma : chroma sampling factors decides: (1,1), (2,1) and (2,2) are the first three colour layouts, (1,2) is
+// JPEG_440 (libjpeg's h1v2 fancy upsampling: 4:4:0, what a losslessly rotated 4:2:2 file becomes), and every other
+// integral pair of ratios 1..4 is JPEG_BOX (libjpeg's integral upsampling: each chroma sample replicated over
+// rh x rv pixels; 4:1:1, 4:1:0, ...), which reads JpegDesc::rh / rv.
+enum JpegLayout : int32_t { JPEG_GRAY = 0, JPEG_444 = 1, JPEG_422 = 2, JPEG_420 = 3, JPEG_440 = 4, JPEG_BOX = 5 };
+
+// jpeg_color_kernel knows the layouts up to JPEG_420 and the YCbCr transform only; an image beyond them needs the
+// kernels built on color_quad (jpeg_idct.hip).
+inline bool jpeg_needs_general(int layout, bool rgb_coded) { return layout > JPEG_420 || rgb_coded; }
 
 struct JpegCompDesc {
   int32_t h, v;       // sampling factors
@@ -31,7 +39,10 @@ struct JpegDesc {
   // compact payload (runtime/jpeg_decode.h jpeg_decode_compact; comp[].coef_off unused): per block a uint64
   // zigzag mask at cmask_off, a uint32 first-value index at cvoff_off, int16 values in zigzag order at cval_off
   int64_t cmask_off, cvoff_off, cval_off;
-  int32_t compact, pad2_;
+  int32_t compact;
+  uint8_t rh, rv;        // JPEG_BOX: pixels per chroma sample along x / y (1..4); other layouts imply theirs
+  uint8_t no_transform;  // 1: the three components are R, G, B (libjpeg's JCS_RGB); 0: YCbCr -> RGB
+  uint8_t pad2_;
 };
 static_assert(sizeof(JpegDesc) == 576, "JpegDesc layout is shared with the kernels");
 

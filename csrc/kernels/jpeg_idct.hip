@@ -11,9 +11,9 @@
 //                       loaded once per lane, fancy upsampling (h2v2 / h2v1 / none) + YCbCr->RGB, three 4-byte
 //                       stores.  grid (pixels / 1024, images), grid-stride over rows x quads.
 //
-// A batch that holds an image with an EXIF orientation other than 1 launches jpeg_color_oriented_kernel in
-// place of jpeg_color_kernel (the host knows from the descriptors it built); every other batch launches exactly
-// the two kernels above.  The oriented kernel computes each quad with the same color_quad and only places it
+// A batch that holds an image with an EXIF orientation other than 1, a layout beyond JPEG_420 (4:4:0, 4:1:1, ...:
+// jpeg_desc.h) or RGB-coded components launches jpeg_color_oriented_kernel in place of jpeg_color_kernel (the host
+// knows from the descriptors it built); every other batch launches exactly the two kernels above.  The oriented kernel computes each quad with the same color_quad and only places it
 // differently (see its comment), so its pixels are those of the plain kernel, moved.
 //
 // jpeg_reconstruct_ragged launches the same two stages as jpeg_idct_ragged_kernel and jpeg_color_ragged_kernel over
@@ -151,9 +151,10 @@ __device__ __forceinline__ ChromaRow chroma_row(const uint8_t* __restrict__ row,
 __device__ __forceinline__ int quad_c(int i) { return i < 2 ? 1 : 2; }
 __device__ __forceinline__ int quad_n(int i) { return i == 0 ? 0 : i == 1 ? 2 : i == 2 ? 1 : 3; }
 
-// The kernel of every batch without an EXIF orientation, i.e. of the whole benchmark workload.  It is kept as one
-// self-contained body, so its code object does not move when the oriented kernel below changes; color_quad is the
-// same per-quad code as a function, for the oriented kernel.
+// The kernel of every batch without an EXIF orientation, a layout beyond JPEG_420 or an RGB-coded image, i.e. of
+// the whole benchmark workload.  It is kept as one self-contained body, so its code object does not move when the
+// oriented kernel below changes; color_quad is the same per-quad code as a function, for the oriented kernel, plus
+// the layouts and the identity transform that only that kernel and the ragged one serve.
 __global__ __launch_bounds__(256) void jpeg_color_kernel(const JpegDesc* __restrict__ descs, uint8_t* __restrict__ pool) {
   const JpegDesc& d = descs[blockIdx.y];
   const int W = d.width, H = d.height, layout = d.layout;
@@ -243,7 +244,7 @@ __device__ __forceinline__ void color_quad(const JpegDesc& d, const uint8_t* __r
         const ChromaRow r = chroma_row(cp + (int64_t)y * cs, 2 * q, C.cw);
 #pragma unroll
         for (int i = 0; i < 4; ++i) dst[i] = jpegm::fancy_h2v1(r.v[quad_c(i)], r.v[quad_n(i)], i & 1);
-      } else {
+      } else if (layout == JPEG_420) {
         const int cy = y >> 1;
         const int ny = (y & 1) ? min(cy + 1, C.ch - 1) : max(cy - 1, 0);
         const ChromaRow a = chroma_row(cp + (int64_t)cy * cs, 2 * q, C.cw);
@@ -251,10 +252,32 @@ __device__ __forceinline__ void color_quad(const JpegDesc& d, const uint8_t* __r
 #pragma unroll
         for (int i = 0; i < 4; ++i)
           dst[i] = jpegm::fancy_h2v2(a.v[quad_c(i)], a.v[quad_n(i)], b.v[quad_c(i)], b.v[quad_n(i)], i & 1);
+      } else if (layout == JPEG_440) {
+        // chroma as wide as luma (equal h, so the same row stride): the quad's columns are one aligned dword of
+        // the nearest chroma row and one of its vertical neighbour, both rows clamped into the component
+        const int cy = y >> 1;
+        const int ny = (y & 1) ? min(cy + 1, C.ch - 1) : max(cy - 1, 0);
+        const uint32_t wa = *reinterpret_cast<const uint32_t*>(cp + (int64_t)cy * cs + x0);
+        const uint32_t wb = *reinterpret_cast<const uint32_t*>(cp + (int64_t)ny * cs + x0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          dst[i] = jpegm::fancy_h1v2((int)((wa >> (8 * i)) & 0xFF), (int)((wb >> (8 * i)) & 0xFF), y & 1);
+      } else {
+        // JPEG_BOX: one chroma byte per rh pixels of row y / rv; the column is clamped into the component like
+        // chroma_row's, which only the pixels past the width (computed, never stored) can need
+        const int rh = d.rh, rv = d.rv;
+        const uint8_t* row = cp + (int64_t)min(jpegm::box_coord(y, rv), C.ch - 1) * cs;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dst[i] = row[min(jpegm::box_coord(x0 + i, rh), C.cw - 1)];
       }
     }
+    if (d.no_transform) {  // RGB-coded: uniform per image, like the layout
 #pragma unroll
-    for (int i = 0; i < 4; ++i) jpegm::ycc_to_rgb((int)((yw >> (8 * i)) & 0xFF), cb[i], cr[i], px + 3 * i);
+      for (int i = 0; i < 4; ++i) jpegm::rgb_identity((int)((yw >> (8 * i)) & 0xFF), cb[i], cr[i], px + 3 * i);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) jpegm::ycc_to_rgb((int)((yw >> (8 * i)) & 0xFF), cb[i], cr[i], px + 3 * i);
+    }
   }
 }
 
@@ -582,14 +605,14 @@ void jpeg_reconstruct_ragged(const JpegDesc* d_descs, uint8_t* d_pool, int n_ima
 }
 
 void jpeg_reconstruct(const JpegDesc* d_descs, uint8_t* d_pool, int n_images, int max_blocks, int64_t max_pixels,
-                      hipStream_t s, bool oriented) {
+                      hipStream_t s, bool general) {
   if (n_images <= 0) return;
   const dim3 g1((unsigned)((max_blocks + kBlocksPerGroup - 1) / kBlocksPerGroup), (unsigned)n_images);
   if (max_blocks > 0) hipLaunchKernelGGL(jpeg_idct_kernel, g1, dim3(256), 0, s, d_descs, d_pool);
   // one lane per 4-pixel quad of a row, grid-stride over the image's rows x quads
   const dim3 g2((unsigned)std::max<int64_t>(1, (max_pixels + 1023) / 1024), (unsigned)n_images);
   if (max_pixels <= 0) return;
-  if (oriented) hipLaunchKernelGGL(jpeg_color_oriented_kernel, g2, dim3(256), 0, s, d_descs, d_pool);
+  if (general) hipLaunchKernelGGL(jpeg_color_oriented_kernel, g2, dim3(256), 0, s, d_descs, d_pool);
   else hipLaunchKernelGGL(jpeg_color_kernel, g2, dim3(256), 0, s, d_descs, d_pool);
 }
 

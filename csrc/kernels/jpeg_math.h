@@ -9,9 +9,9 @@
 // PIL's (tests/test_jpeg_native.py pins that on the curated workload).
 //
 // Attribution: the IDCT below follows the structure and fixed-point constants of libjpeg's jidctint.c (islow), the
-// chroma upsampling that of jdsample.c (h2v1 / h2v2 "fancy" upsampling) and the colour conversion that of
-// jdcolor.c (ycc_rgb_convert).  Bit-exactness with PIL / libjpeg-turbo requires exactly that arithmetic.  This
-// software is based in part on the work of the Independent JPEG Group (see NOTICE at the repository root).
+// chroma upsampling that of jdsample.c (h2v1 / h2v2 / h1v2 "fancy" upsampling and the integral replication of
+// int_upsample) and the colour conversion that of jdcolor.c (ycc_rgb_convert; rgb_rgb_convert for RGB-coded files).
+// Bit-exactness with PIL / libjpeg-turbo requires exactly that arithmetic.  This software is based in part on the work of the Independent JPEG Group (see NOTICE at the repository root).
 //
 // Everything is plain integer math on values the caller supplies; there is no table and no memory access, so
 // the same functions run per lane in the HIP kernel and per pixel in the host reference.
@@ -110,6 +110,21 @@ ARENA_JHD int fancy_h2v2(int c00, int c01, int c10, int c11, int x_odd) {
 
 // h2v1 (4:2:2): jdsample.c h2v1_fancy_upsample; `cn` is the horizontal neighbour on the output pixel's side.
 ARENA_JHD int fancy_h2v1(int c, int cn, int x_odd) { return (c * 3 + cn + (x_odd ? 2 : 1)) >> 2; }
+
+// h1v2 (4:4:0): jdsample.c h1v2_fancy_upsample; `cn` is the vertical neighbour on the output row's side: the row above
+// for even y, below for odd y, the edge row itself outside the component.  There is no narrow-component exception.
+ARENA_JHD int fancy_h1v2(int c, int cn, int y_odd) { return (c * 3 + cn + (y_odd ? 2 : 1)) >> 2; }
+
+// Integral upsampling (jdsample.c int_upsample): chroma sample p / r covers output pixels p .. p + r - 1 along an
+// axis with ratio r (1..4), whatever the component's width.
+ARENA_JHD int box_coord(int p, int r) { return r == 1 ? p : r == 2 ? p >> 1 : r == 4 ? p >> 2 : p / 3; }
+
+// RGB-coded file (jdcolor.c rgb_rgb_convert): the three components are the pixel.
+ARENA_JHD void rgb_identity(int c0, int c1, int c2, uint8_t* rgb) {
+  rgb[0] = (uint8_t)c0;
+  rgb[1] = (uint8_t)c1;
+  rgb[2] = (uint8_t)c2;
+}
 
 // YCbCr -> RGB (jdcolor.c ycc_rgb_convert with its build_ycc_rgb_table entries, SCALEBITS 16).
 ARENA_JHD void ycc_to_rgb(int y, int cb, int cr, uint8_t* rgb) {

@@ -494,11 +494,12 @@ void stamp(void* dst, hipStream_t s);
 // Device half of the split JPEG decoder (csrc/kernels/jpeg_idct.hip): for n_images descriptors (jpeg_desc.h)
 // reconstruct packed RGB at d_pool + desc.rgb_off from the quantized coefficient blocks at d_pool +
 // comp.coef_off (sample planes at d_pool + comp.plane_off as scratch).  max_blocks / max_pixels: the largest
-// total_blocks / width * height over the batch (grid sizes).  `oriented`: some descriptor has an EXIF
-// orientation other than 1, so the colour stage runs as the oriented kernel; false launches the plain kernels.
+// total_blocks / width * height over the batch (grid sizes).  `general`: some descriptor has an EXIF
+// orientation other than 1, a layout beyond JPEG_420 or RGB-coded components (jpeg_needs_general), so the colour
+// stage runs as the oriented kernel, which is built on color_quad; false launches the plain kernels.
 struct JpegDesc;
 void jpeg_reconstruct(const JpegDesc* d_descs, uint8_t* d_pool, int n_images, int max_blocks, int64_t max_pixels,
-                      hipStream_t s, bool oriented = false);
+                      hipStream_t s, bool general = false);
 // The same reconstruction over a ragged grid: one workgroup per unit of real work (jpeg_desc.h), for batches whose
 // image sizes differ widely (arm B's crops).  The descriptors carry their first units (jpeg_ragged_plan, which also
 // gives the two totals); no descriptor may have an EXIF orientation other than 1.  Writes the bytes jpeg_reconstruct

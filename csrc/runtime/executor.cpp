@@ -1191,6 +1191,7 @@ int Executor::submit(const std::vector<InputImage>& imgs) {
   int nj = 0, max_blocks = 0;
   int64_t max_pix = 0;
   bool oriented = false;  // some JPEG of the batch carries an EXIF orientation: the oriented colour kernel runs
+  bool general = false;   // ... or a layout / colour transform that only color_quad knows: the same kernel
   // packed coefficients sit contiguously right after the host-packed inputs, inside the one staging DMA
   std::vector<size_t> coef_at(n, 0);
   {
@@ -1220,6 +1221,7 @@ int Executor::submit(const std::vector<InputImage>& imgs) {
     max_blocks = std::max(max_blocks, jdesc[nj].total_blocks);
     max_pix = std::max(max_pix, (int64_t)im.h * im.w);
     oriented |= ji.orientation > 1;
+    general |= ji.orientation > 1 || jpeg_needs_general(ji.layout, ji.rgb_coded);
     ++nj;
     off = end;
   }
@@ -1257,7 +1259,7 @@ int Executor::submit(const std::vector<InputImage>& imgs) {
                               rplan.idct_units, rplan.color_units, sl.stream);
     else
       jpeg_reconstruct((const JpegDesc*)(sl.d_in + jpeg_desc_off()), sl.d_in + in_bytes_meta(), nj, max_blocks, max_pix,
-                       sl.stream, oriented);
+                       sl.stream, general);
     ARENA_HIP_CHECK(hipGetLastError());
   }
   // frames exported to another buffer on this device (arm B's IPC ring): device to device, in stream order

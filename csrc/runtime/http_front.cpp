@@ -1505,6 +1505,7 @@ void HttpFrontEnd::native_decode(DecodeTask& t) {
     ++stats_.native_decoded;
     if (ji.orientation > 1) ++stats_.oriented_decoded;
     if (ji.progressive) ++stats_.progressive_decoded;
+    if (ji.multiscan || jpeg_needs_general(ji.layout, ji.rgb_coded)) ++stats_.layout_decoded;
     stats_.cpu_decode_ms += thread_cpu_ms() - c0;
   }
   {

@@ -152,6 +152,8 @@ struct FrontStats {
   int64_t native_decoded = 0, fallback_decoded = 0;  // uploads decoded by the split decoder / the PIL pool
   int64_t oriented_decoded = 0;  // of native_decoded: uploads with an EXIF orientation other than 1
   int64_t progressive_decoded = 0;  // of native_decoded: progressive (SOF2) uploads
+  // of native_decoded: uploads in a layout beyond 4:2:0 (4:4:0, 4:1:1, ...), sequential in several scans, or RGB-coded
+  int64_t layout_decoded = 0;
   int64_t bodies_recycled = 0, bodies_allocated = 0;  // request bodies served by the body pool / newly grown
   int64_t bodies_retained_bytes = 0, bodies_budget_bytes = 0;  // capacity the pool holds now / may hold
   int64_t bodies_over_budget = 0;                     // returned bodies freed because of the byte budget

@@ -130,6 +130,7 @@ struct BitReader {
   int64_t pad = 0;         // zero bytes fed because the data ended without a marker
   int64_t zfill = 0;       // zero bytes fed after a marker cut the segment short
   bool truncated = false;  // some of the `pad` bits were consumed (PIL: "image file is truncated")
+  bool bad_code = false;   // decode() met bits that match no code (libjpeg warns)
 
   __attribute__((always_inline)) inline void refill() {
     if (!marker && end - p >= 8) {
@@ -205,6 +206,7 @@ struct BitReader {
       }
     }
     // no code matches (corrupt data): libjpeg warns and yields symbol 0; consume 16 bits so the scan advances
+    bad_code = true;
     skip(16);
     return 0;
   }
@@ -488,14 +490,24 @@ JpegStatus jpeg_parse(const uint8_t* data, size_t n, JpegInfo& info, std::string
         err = "Failed to decode image: scan before frame header";
         return JpegStatus::Corrupt;
       }
-      if (info.progressive) {  // the scans are walked by the decode functions (decode_progressive)
+      if (info.progressive) {  // the scans are walked by the decode functions (decode_scans)
         info.first_sos = pos - len;
         info.scan_begin = pos;
         break;
       }
       const int ns = sl >= 1 ? seg[0] : 0;
+      // a first scan that is not all components in the frame's order: the walker takes every scan, as for a
+      // progressive file, and decides there what it cannot vouch for
+      bool in_order = ns == info.ncomp && sl >= 1 + 2 * (size_t)ns + 3;
+      for (int i = 0; in_order && i < ns; ++i) in_order = seg[1 + 2 * i] == info.comp_id[i];
+      if (!in_order && info.ncomp > 1 && ns >= 1 && ns <= info.ncomp && sl >= 1 + 2 * (size_t)ns + 3) {
+        info.multiscan = true;
+        info.first_sos = pos - len;
+        info.scan_begin = pos;
+        break;
+      }
       if (ns != info.ncomp) {
-        err = "multi-scan (non-interleaved) JPEG";
+        err = "scan component count";
         return JpegStatus::Unsupported;
       }
       if (sl < 1 + 2 * (size_t)ns + 3) {
@@ -525,17 +537,11 @@ JpegStatus jpeg_parse(const uint8_t* data, size_t n, JpegInfo& info, std::string
     }
     // every other marker (APPn, COM, ...) is skipped by its length
   }
-  // colour space as libjpeg guesses it (jdapimin.c default_decompress_parms): only YCbCr is reconstructed here
-  if (info.ncomp == 3) {
-    if (!saw_jfif && adobe && adobe_transform == 0) {
-      err = "RGB-coded JPEG (Adobe transform 0)";
-      return JpegStatus::Unsupported;
-    }
-    if (!saw_jfif && !adobe && info.comp_id[0] == 'R' && info.comp_id[1] == 'G' && info.comp_id[2] == 'B') {
-      err = "RGB-coded JPEG";
-      return JpegStatus::Unsupported;
-    }
-  }
+  // colour space as libjpeg guesses it (jdapimin.c default_decompress_parms): JFIF means YCbCr; else an Adobe
+  // segment decides by its transform (0: RGB); else the component ids R, G, B mean RGB; everything else is YCbCr
+  if (info.ncomp == 3 && !saw_jfif)
+    info.rgb_coded = adobe ? adobe_transform == 0
+                           : info.comp_id[0] == 'R' && info.comp_id[1] == 'G' && info.comp_id[2] == 'B';
   for (int c = 0; c < info.ncomp; ++c) {
     if (!qpresent[info.tq[c]]) {
       err = "Failed to decode image: missing quantization table";
@@ -553,12 +559,20 @@ JpegStatus jpeg_parse(const uint8_t* data, size_t n, JpegInfo& info, std::string
       err = "chroma sampling";
       return JpegStatus::Unsupported;
     }
+    // the upsampler libjpeg picks (jdsample.c jinit_upsampler): fancy for 2:1 horizontally with 1:1 or 2:1
+    // vertically and for 1:1 with 2:1, integral replication for every other ratio
     const int rh = y.h / cb.h, rv = y.v / cb.v;
+    info.rh = rh;
+    info.rv = rv;
     if (rh == 1 && rv == 1) info.layout = JPEG_444;
     else if (rh == 2 && rv == 1) info.layout = JPEG_422;
     else if (rh == 2 && rv == 2) info.layout = JPEG_420;
-    else {
-      err = "chroma sampling";
+    else if (rh == 1 && rv == 2) info.layout = JPEG_440;
+    else info.layout = JPEG_BOX;
+    // libjpeg refuses an interleaved scan whose MCU holds more than 10 blocks (D_MAX_BLOCKS_IN_MCU); PIL reports
+    // it.  A file whose scans are walked is checked scan by scan.
+    if (!info.progressive && !info.multiscan && y.h * y.v + cb.h * cb.v + cr.h * cr.v > 10) {
+      err = "MCU larger than 10 blocks";
       return JpegStatus::Unsupported;
     }
   }
@@ -576,7 +590,7 @@ JpegStatus jpeg_parse(const uint8_t* data, size_t n, JpegInfo& info, std::string
       d.bw = info.mcux * d.h;
       d.bh = info.mcuy * d.v;
     }
-    if (info.layout != JPEG_GRAY && info.layout != JPEG_444 && c > 0 && d.cw <= 2) {
+    if ((info.layout == JPEG_422 || info.layout == JPEG_420) && c > 0 && d.cw <= 2) {
       err = "chroma narrower than 3 samples (libjpeg switches to box upsampling)";
       return JpegStatus::Unsupported;
     }
@@ -631,11 +645,6 @@ struct TableCache {
 // ---- progressive files (SOF2, T.81 Annex G; the behaviour matched is libjpeg's jdphuff.c) -----------------------
 
 inline bool fits16(int v) { return v >= -32768 && v <= 32767; }
-
-JpegStatus hand_back(std::string& err, const char* why) {
-  err = std::string("progressive JPEG outside the split decoder: ") + why;
-  return JpegStatus::Unsupported;
-}
 
 // One Huffman symbol as BitReader::decode reads it, but -1 where no code matches (libjpeg warns and goes on with a
 // zero: not a result to vouch for).
@@ -762,8 +771,14 @@ inline bool prog_ac_refine(BitReader& br, const HuffTable& t, int ss, int se, in
   return true;
 }
 
-// All scans of a progressive file into dense blocks (contract in jpeg_decode.h, jpeg_decode_coefs).
-JpegStatus decode_progressive(const uint8_t* data, size_t n, const JpegInfo& info, int16_t* coef, std::string& err) {
+// All scans of a progressive file, or of a sequential one that comes in several scans (info.multiscan: every scan
+// codes whole blocks of its components), into dense blocks (contract in jpeg_decode.h, jpeg_decode_coefs).
+JpegStatus decode_scans(const uint8_t* data, size_t n, const JpegInfo& info, int16_t* coef, std::string& err) {
+  const bool seq = !info.progressive;
+  auto hand_back = [seq](std::string& e, const char* why) {
+    e = std::string(seq ? "multi-scan" : "progressive") + " JPEG outside the split decoder: " + why;
+    return JpegStatus::Unsupported;
+  };
   thread_local std::unique_ptr<TableCache> cache;
   if (!cache) cache.reset(new TableCache());
   std::memset(coef, 0, (size_t)info.coef_count * sizeof(int16_t));
@@ -776,6 +791,7 @@ JpegStatus decode_progressive(const uint8_t* data, size_t n, const JpegInfo& inf
   // successive-approximation bit each coefficient is down to: -1 = never sent
   int8_t sent[kJpegMaxComp][64];
   std::memset(sent, -1, sizeof sent);
+  bool coded[kJpegMaxComp] = {false, false, false};  // sequential: the component had its scan
   const char* const kTruncated = "Failed to decode image: image file is truncated";
   size_t pos = info.first_sos;
   for (int nscan = 1;; ++nscan) {
@@ -813,11 +829,21 @@ JpegStatus decode_progressive(const uint8_t* data, size_t n, const JpegInfo& inf
     }
     const uint8_t* sp = seg + 1 + 2 * ns;
     const int ss = sp[0], se = sp[1], ah = sp[2] >> 4, al = sp[2] & 15;
-    // G.1.1.1.1
-    if (ss == 0 ? se != 0 : (ns != 1 || ss > se || se > 63)) return hand_back(err, "spectral selection");
-    if ((ah != 0 && ah != al + 1) || al > 13) return hand_back(err, "successive approximation");
+    if (seq) {
+      // libjpeg only warns about other parameters in a sequential scan and decodes whole blocks all the same
+      if (ss != 0 || se != 63 || ah != 0 || al != 0) return hand_back(err, "spectral selection of a sequential scan");
+      // it outputs whatever the scans left in a component: exact only when each had exactly one
+      for (int i = 0; i < ns; ++i) {
+        if (coded[ci[i]]) return hand_back(err, "component coded twice");
+        coded[ci[i]] = true;
+      }
+    } else {
+      // G.1.1.1.1
+      if (ss == 0 ? se != 0 : (ns != 1 || ss > se || se > 63)) return hand_back(err, "spectral selection");
+      if ((ah != 0 && ah != al + 1) || al > 13) return hand_back(err, "successive approximation");
+    }
     if (ns > 1 && mcu_blocks > 10) return hand_back(err, "MCU larger than 10 blocks");
-    for (int i = 0; i < ns; ++i) {
+    for (int i = 0; !seq && i < ns; ++i) {
       int8_t* s = sent[ci[i]];
       if (ss > 0 && s[0] < 0) return hand_back(err, "AC scan before the component's DC");
       for (int k = ss; k <= se; ++k) {
@@ -827,8 +853,22 @@ JpegStatus decode_progressive(const uint8_t* data, size_t n, const JpegInfo& inf
       }
     }
     const HuffTable* tab[kJpegMaxComp] = {};
+    const HuffTable* actab[kJpegMaxComp] = {};  // sequential: a block takes both tables
     ++cache->gen;
-    if (ss > 0 || ah == 0) {  // a DC refinement scan carries raw bits only
+    if (seq) {
+      for (int i = 0; i < ns; ++i) {
+        if (td[i] > 3 || ta[i] > 3 || !dc[td[i]].present || !ac[ta[i]].present) {
+          err = "Failed to decode image: missing Huffman table";
+          return JpegStatus::Corrupt;
+        }
+        tab[i] = cache->get(dc[td[i]], false);
+        actab[i] = tab[i] ? cache->get(ac[ta[i]], true) : nullptr;
+        if (!tab[i] || !actab[i]) {
+          err = "Failed to decode image: bad Huffman table";
+          return JpegStatus::Corrupt;
+        }
+      }
+    } else if (ss > 0 || ah == 0) {  // a DC refinement scan carries raw bits only
       for (int i = 0; i < ns; ++i) {
         const int th = ss > 0 ? ta[i] : td[i];
         if (th > 3 || !(ss > 0 ? ac : dc)[th].present) {
@@ -850,7 +890,7 @@ JpegStatus decode_progressive(const uint8_t* data, size_t n, const JpegInfo& inf
     const JpegCompDesc& d0 = info.comp[ci[0]];
     const int sbw = single ? (d0.cw + 7) / 8 : info.mcux, sbh = single ? (d0.ch + 7) / 8 : info.mcuy;
     const int64_t n_mcu = (int64_t)sbw * sbh;
-    const int kind = ss == 0 ? (ah == 0 ? 0 : 1) : (ah == 0 ? 2 : 3);
+    const int kind = seq ? 4 : ss == 0 ? (ah == 0 ? 0 : 1) : (ah == 0 ? 2 : 3);
     BitReader br{data + pos, data + n};
     int pred[kJpegMaxComp] = {0, 0, 0};
     int eobrun = 0;
@@ -860,7 +900,9 @@ JpegStatus decode_progressive(const uint8_t* data, size_t n, const JpegInfo& inf
         case 0: return prog_dc_first(br, *tab[i], pred[i], al, blk);
         case 1: prog_dc_refine(br, al, blk); return true;
         case 2: return prog_ac_first(br, *tab[i], ss, se, al, eobrun, blk);
-        default: return prog_ac_refine(br, *tab[i], ss, se, al, eobrun, blk);
+        case 3: return prog_ac_refine(br, *tab[i], ss, se, al, eobrun, blk);
+        // a whole block as a baseline scan codes it; bits that match no code make libjpeg warn
+        default: return decode_block(br, *tab[i], *actab[i], pred[i], blk) && !br.bad_code;
       }
     };
     int next_rst = 0;
@@ -950,6 +992,11 @@ JpegStatus decode_progressive(const uint8_t* data, size_t n, const JpegInfo& inf
     if (eoi) break;
     pos = q;
   }
+  if (seq) {
+    for (int c = 0; c < info.ncomp; ++c)
+      if (!coded[c]) return hand_back(err, "component never coded");
+    return JpegStatus::Ok;
+  }
   // libjpeg smooths (and PIL returns the smoothed image) when the file ends before every coefficient is exact
   for (int c = 0; c < info.ncomp; ++c)
     for (int k = 0; k < 64; ++k)
@@ -959,7 +1006,7 @@ JpegStatus decode_progressive(const uint8_t* data, size_t n, const JpegInfo& inf
 }  // namespace
 
 JpegStatus jpeg_decode_coefs(const uint8_t* data, size_t n, const JpegInfo& info, int16_t* coef, std::string& err) {
-  if (info.progressive) return decode_progressive(data, n, info, coef, err);
+  if (info.progressive || info.multiscan) return decode_scans(data, n, info, coef, err);
   thread_local std::unique_ptr<TableCache> cache;
   if (!cache) cache.reset(new TableCache());
   const HuffTable* dcp[kJpegMaxComp] = {};
@@ -1094,10 +1141,10 @@ void dense_to_compact(JpegInfo& info, const int16_t* coef, uint8_t* out) {
 }  // namespace
 
 JpegStatus jpeg_decode_compact(const uint8_t* data, size_t n, JpegInfo& info, uint8_t* out, std::string& err) {
-  if (info.progressive) {  // the scans refine dense blocks; the payload is packed after the last one
+  if (info.progressive || info.multiscan) {  // the scans fill dense blocks; the payload is packed after the last one
     thread_local std::vector<int16_t> dense;
     dense.resize((size_t)info.coef_count);
-    const JpegStatus st = decode_progressive(data, n, info, dense.data(), err);
+    const JpegStatus st = decode_scans(data, n, info, dense.data(), err);
     if (st == JpegStatus::Ok) dense_to_compact(info, dense.data(), out);
     if (dense.capacity() > ((size_t)16 << 20)) std::vector<int16_t>().swap(dense);  // do not pin a huge frame's
     return st;
@@ -1264,15 +1311,23 @@ void jpeg_coefs_to_rgb(const JpegInfo& info, const int16_t* coef, uint8_t* rgb) 
           const int cx = x >> 1, xo = x & 1;
           const int nx = xo ? std::min(cx + 1, C.cw - 1) : std::max(cx - 1, 0);
           cc[k] = fancy_h2v1(cp[(int64_t)y * cs + cx], cp[(int64_t)y * cs + nx], xo);
-        } else {
+        } else if (info.layout == JPEG_420) {
           const int cx = x >> 1, xo = x & 1, cy = y >> 1;
           const int nx = xo ? std::min(cx + 1, C.cw - 1) : std::max(cx - 1, 0);
           const int ny = (y & 1) ? std::min(cy + 1, C.ch - 1) : std::max(cy - 1, 0);
           cc[k] = fancy_h2v2(cp[(int64_t)cy * cs + cx], cp[(int64_t)cy * cs + nx], cp[(int64_t)ny * cs + cx],
                              cp[(int64_t)ny * cs + nx], xo);
+        } else if (info.layout == JPEG_440) {
+          const int cy = y >> 1;
+          const int ny = (y & 1) ? std::min(cy + 1, C.ch - 1) : std::max(cy - 1, 0);
+          cc[k] = fancy_h1v2(cp[(int64_t)cy * cs + x], cp[(int64_t)ny * cs + x], y & 1);
+        } else {  // JPEG_BOX
+          const int cx = std::min(box_coord(x, info.rh), C.cw - 1), cy = std::min(box_coord(y, info.rv), C.ch - 1);
+          cc[k] = cp[(int64_t)cy * cs + cx];
         }
       }
-      ycc_to_rgb(yy, cc[0], cc[1], o);
+      if (info.rgb_coded) rgb_identity(yy, cc[0], cc[1], o);
+      else ycc_to_rgb(yy, cc[0], cc[1], o);
     }
   }
 }
@@ -1285,6 +1340,9 @@ JpegDesc jpeg_device_desc(const JpegInfo& info, int64_t coef_base, int64_t plane
   d.width = info.width;
   d.height = info.height;
   d.orientation = info.orientation;
+  d.rh = (uint8_t)info.rh;
+  d.rv = (uint8_t)info.rv;
+  d.no_transform = info.rgb_coded ? 1 : 0;
   d.rgb_off = rgb_off;
   int64_t total = 0;
   for (int c = 0; c < info.ncomp; ++c) {

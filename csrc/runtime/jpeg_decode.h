@@ -8,15 +8,18 @@
 // work PIL does in one call is cut where the data is smallest and the arithmetic least parallel: the bit
 // serial Huffman stream stays on a host thread, the per-pixel math moves to the GPU.
 //
-// Scope: baseline / extended-sequential Huffman (SOF0, SOF1), 8-bit samples, one interleaved scan with all
-// components, 1 (grayscale) or 3 (YCbCr) components in 4:4:4, 4:2:2 or 4:2:0, restart intervals; and, when the
-// progressive switch is on (ARENA_JPEG_PROGRESSIVE, default 0, or the `progressive` argument of jpeg_parse),
-// progressive Huffman files (SOF2, T.81 Annex G) of the same frame geometry whose scans send every coefficient of
-// every component down to bit 0.  Everything else — arithmetic-coded, 12-bit, CMYK, RGB-coded, multi-scan
-// sequential, other samplings, progressive files with the switch off, with an incomplete or inconsistent
-// progression, more than kJpegMaxScans scans or a DQT between scans — is reported as Unsupported and the caller
-// sends the upload to the PIL fallback (server/decode_pool.py).  For a progressive file Unsupported can also come
-// from the decode functions, after jpeg_parse said Ok: callers route it to the same fallback.  The same
+// Scope: baseline / extended-sequential Huffman (SOF0, SOF1), 8-bit samples, 1 (grayscale) or 3 components (YCbCr,
+// or RGB-coded as libjpeg recognises it) whose chroma factors are equal and divide the luma's (4:4:4, 4:2:2, 4:2:0,
+// 4:4:0, 4:1:1, 4:1:0, ...: JpegLayout), one interleaved scan or several scans that code every component exactly
+// once, restart intervals; and, when the progressive switch is on (ARENA_JPEG_PROGRESSIVE, default 0, or the
+// `progressive` argument of jpeg_parse), progressive Huffman files (SOF2, T.81 Annex G) of the same frame geometry
+// whose scans send every coefficient of every component down to bit 0.  Everything else — arithmetic-coded,
+// lossless, 12-bit, CMYK / YCCK, a height from DNL, luma below the maximum factor or unequal chroma factors, 4:2:2
+// / 4:2:0 chroma narrower than 3 samples, an interleaved MCU of more than 10 blocks, progressive files with the
+// switch off, with an incomplete or inconsistent progression, more than kJpegMaxScans scans or a DQT between scans
+// — is reported as Unsupported and the caller sends the upload to the PIL fallback (server/decode_pool.py).  For a
+// file whose scans are walked (progressive, or sequential in several scans) Unsupported can also come from the
+// decode functions, after jpeg_parse said Ok: callers route it to the same fallback.  The same
 // reconstruction arithmetic is available on the host (jpeg_coefs_to_rgb) as the bit-exact reference of the
 // kernels and as a host-only decode.
 #pragma once
@@ -39,6 +42,9 @@ struct JpegInfo {
   int width = 0, height = 0, ncomp = 0;
   int hmax = 1, vmax = 1, mcux = 0, mcuy = 0;
   int layout = -1;
+  // luma : chroma sampling ratio (1..4 each; 1 for grey), and whether the components are R, G, B (no YCbCr step)
+  int rh = 1, rv = 1;
+  bool rgb_coded = false;
   // EXIF orientation (1..8; 1 when absent or not well-formed, see jpeg_parse) and the size of the oriented
   // output: width and height swapped for 5..8.  width / height stay the stored frame's.
   int orientation = 1;
@@ -55,6 +61,9 @@ struct JpegInfo {
   // segment; DHT, DRI and further SOS follow between scans).  restart_interval and dc / ac are the state there.
   bool progressive = false;
   size_t first_sos = 0;
+  // SOF0/1 whose first scan is not all components in frame order: walked from `first_sos` in the same way, every
+  // scan a full-block one
+  bool multiscan = false;
   // compact payload (jpeg_decode_compact): its bytes and the byte offsets of its three arrays; -1 = dense int16
   int64_t compact_bytes = -1;
   int64_t cmask_off = 0, cvoff_off = 0, cval_off = 0;
@@ -101,6 +110,11 @@ JpegStatus jpeg_parse(const uint8_t* data, size_t n, JpegInfo& info, std::string
 // a code that matches nothing, a refinement symbol of another magnitude than 1, a segment that a marker cuts short
 // or that leaves bytes over, a restart marker that is missing or not the expected RSTn.  (Baseline scans keep
 // their zero-bit padding of a segment cut short.)
+//
+// A sequential file in several scans (info.multiscan) goes through the same walker with full-block scans (Ss 0,
+// Se 63, Ah = Al = 0; anything else is handed back) and the same strictness about damaged data.  libjpeg does not
+// smooth such a file; it outputs whatever it has, so the result is Ok only when every component was coded by exactly
+// one scan: a component coded twice or never is Unsupported.
 JpegStatus jpeg_decode_coefs(const uint8_t* data, size_t n, const JpegInfo& info, int16_t* coef, std::string& err);
 
 // The same scan into the compact payload the split decoder ships (3-4x fewer bytes than the dense blocks at q90:
@@ -108,8 +122,8 @@ JpegStatus jpeg_decode_coefs(const uint8_t* data, size_t n, const JpegInfo& info
 // row, then 1, 2): a uint64 mask (bit k: the coefficient at zigzag index k is coded), then per block the uint32
 // index of its first value, then the int16 values of every block in zigzag order (16-byte aligned array).  `out`
 // holds jpeg_compact_capacity(info) bytes; on success info.compact_bytes / cmask_off / cvoff_off / cval_off
-// describe what was written.  Status and error messages as jpeg_decode_coefs.  A progressive file is decoded into
-// dense blocks in a thread-local scratch (released after use when above 16 MB) and packed after its last scan.
+// describe what was written.  Status and error messages as jpeg_decode_coefs.  A file whose scans are walked
+// (progressive or multi-scan sequential) is decoded into dense blocks in a thread-local scratch (released after use when above 16 MB) and packed after its last scan.
 JpegStatus jpeg_decode_compact(const uint8_t* data, size_t n, JpegInfo& info, uint8_t* out, std::string& err);
 int64_t jpeg_total_blocks(const JpegInfo& info);
 int64_t jpeg_compact_capacity(const JpegInfo& info);

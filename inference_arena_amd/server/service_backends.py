@@ -83,8 +83,8 @@ class GpuClassifierBackend(ClassifierBackend):
     async def classify_bytes(self, data: bytes, decode):
         """A JPEG crop through the native split decoder (``ARENA_CROP_DECODE=gpu``): Huffman decode on C++ threads,
         pixels reconstructed on the GPU inside the classifier batch, the same pixels PIL decodes.  Crops the
-        decoder hands back (progressive with the switch off, CMYK, subsampled crops no wider than 4 pixels, any
-        other format) go through ``await decode(data)`` and ``classify``'s path; a corrupt crop raises."""
+        decoder hands back (progressive with the switch off, CMYK, 4:2:2 / 4:2:0 crops no wider than 4 pixels,
+        any other format) go through ``await decode(data)`` and ``classify``'s path; a corrupt crop raises."""
         d = await self.batcher.run_jpeg(data, decode, threads=int(os.environ.get("ARENA_INGEST_THREADS", "4")))
         return d["topk_idx"][0], d["topk_logit"][0], d["topk_prob"][0]
 
