@@ -9,11 +9,11 @@
 // ultralytics' C3); unfused here they were four kernels whose 52-105 MB intermediates crossed HBM: ~680 MB of
 // traffic per batch of 32 requests, 155 us (ops 2-5 of profiles/r4d/ops_s6t0_bs32.md).  Here one workgroup
 // owns an 8 x 16 output tile, recomputes the 1x1 stages on a one-pixel halo ring (10 x 18 = 180 pixels, 1.4x
-// their MACs) and keeps T and U in LDS as triple-bf16 planes (v = h + m + l exactly to fp32 rounding, the x3
-// scheme of ir_tile_x3.hip): HBM sees the block input once and the output once.
+// their MACs) and keeps T and U in LDS as triple-bf16 planes (the x3 scheme, x3.h): HBM sees the block input
+// once and the output once.
 //
-// Every GEMM runs on the matrix cores with the six-product split (am bm, al bh, ah bl, am bh, ah bm, ah bh;
-// fp32 accumulation): rows = output channels (A = weights, pre-split at plan time), columns = pixels
+// Every GEMM runs on the matrix cores with the six-product chain of x3.h: rows = output channels (A = weights,
+// pre-split at plan time), columns = pixels
 // (B = activations).  v_mfma_f32_16x16x32_bf16 for K = 32 steps; the 16-deep Bottleneck 1x1 uses
 // v_mfma_f32_16x16x16_bf16 instead of padding K.  The 3x3 packs two taps (2 x 16 channels) per 32-deep K step:
 // 9 taps in 5 steps, the tenth tap's weights are zero.
@@ -22,15 +22,12 @@
 // wb2 [16][3][160] (k = tap * 16 + channel), w3 [32][3][32] — planes h, m, l of each fp32 row; biases fp32.
 #include <stdexcept>
 
-#include "common.h"
 #include "launch.h"
+#include "x3.h"
 
 namespace arena {
 
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int C3X_TH = 8, C3X_TW = 16;                       // output tile
 constexpr int C3X_PH = C3X_TH + 2, C3X_PW = C3X_TW + 2;      // halo tile
@@ -39,50 +36,6 @@ constexpr int C3X_ROWS = (C3X_NPIX + 15) / 16 * 16;          // 192 (12 pixel ti
 constexpr int C3X_TPB = 3 * 32 * 2 + 16;                     // T row: [h 32 | m 32 | l 32] bf16 + pad (13 slots)
 constexpr int C3X_UPB = 3 * 16 * 2 + 16;                     // U row: [h 16 | m 16 | l 16] bf16 + pad (7 slots)
 constexpr int C3X_LDS = C3X_ROWS * (C3X_TPB + C3X_UPB) + 96 * 4;  // + the four bias vectors
-
-__device__ __forceinline__ void c3x_split4(const float* v, bf16x4& h, bf16x4& m, bf16x4& l) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const bf16 th = (bf16)v[i];
-    const float r = v[i] - (float)th;
-    const bf16 tm = (bf16)r;
-    h[i] = th;
-    m[i] = tm;
-    l[i] = (bf16)(r - (float)tm);
-  }
-}
-
-__device__ __forceinline__ void c3x_split8(const float* v, bf16x8& h, bf16x8& m, bf16x8& l) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const bf16 th = (bf16)v[i];
-    const float r = v[i] - (float)th;
-    const bf16 tm = (bf16)r;
-    h[i] = th;
-    m[i] = tm;
-    l[i] = (bf16)(r - (float)tm);
-  }
-}
-
-__device__ __forceinline__ f32x4 c3x_mfma32(const bf16x8& ah, const bf16x8& am, const bf16x8& al, const bf16x8& bh,
-                                            const bf16x8& bm, const bf16x8& bl, f32x4 c) {
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bm, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bm, c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ f32x4 c3x_mfma16(const bf16x4& ah, const bf16x4& am, const bf16x4& al, const bf16x4& bh,
-                                            const bf16x4& bm, const bf16x4& bl, f32x4 c) {
-  c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(am, bm, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(al, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ah, bl, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(am, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ah, bm, c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ah, bh, c, 0, 0, 0);
-}
 
 // one lane's 16-byte piece of each plane of a pre-split weight row (row stride 3 * K bf16)
 __device__ __forceinline__ void c3x_wload8(const bf16* w, int K, int row, int k, bf16x8& h, bf16x8& m, bf16x8& l) {
@@ -164,7 +117,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
       const bool in = xin[i];
       float v[8] = {in ? xa[i].x : 0.f, in ? xa[i].y : 0.f, in ? xa[i].z : 0.f, in ? xa[i].w : 0.f,
                     in ? xb[i].x : 0.f, in ? xb[i].y : 0.f, in ? xb[i].z : 0.f, in ? xb[i].w : 0.f};
-      c3x_split8(v, xh[i], xm[i], xl[i]);
+      x3_split8(v, xh[i], xm[i], xl[i]);
     }
     if (tile + (int)gridDim.x < total) C3X_FETCH(tile + (int)gridDim.x)
 #pragma unroll
@@ -172,12 +125,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
       const int r = (wave + 4 * i) * 16 + col;
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt) {
-        const f32x4 acc = c3x_mfma32(w1h[nt], w1m[nt], w1l[nt], xh[i], xm[i], xl[i], f32x4{0.f, 0.f, 0.f, 0.f});
+        const f32x4 acc = x3_mfma(w1h[nt], w1m[nt], w1l[nt], xh[i], xm[i], xl[i], f32x4{0.f, 0.f, 0.f, 0.f});
         // lane holds channels nt * 16 + 4 kq .. +3 of halo pixel r
         const float4 bb = *(const float4*)(Bs + nt * 16 + 4 * kq);
         float o[4] = {silu(acc[0] + bb.x), silu(acc[1] + bb.y), silu(acc[2] + bb.z), silu(acc[3] + bb.w)};
         bf16x4 h, m, l;
-        c3x_split4(o, h, m, l);
+        x3_split4(o, h, m, l);
         uint8_t* d = Tp + r * C3X_TPB + (nt * 16 + 4 * kq) * 2;
         *(bf16x4*)d = h;
         *(bf16x4*)(d + 64) = m;
@@ -192,15 +145,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
   for (int i = 0; i < 3; ++i) {
     const int r = (wave + 4 * i) * 16 + col;
     const uint8_t* s = Tp + r * C3X_TPB + 8 * kq;
-    const f32x4 acc = c3x_mfma16(w2h, w2m, w2l, *(const bf16x4*)s, *(const bf16x4*)(s + 64),
-                                 *(const bf16x4*)(s + 128), f32x4{0.f, 0.f, 0.f, 0.f});
+    const f32x4 acc = x3_mfma(w2h, w2m, w2l, *(const bf16x4*)s, *(const bf16x4*)(s + 64),
+                              *(const bf16x4*)(s + 128), f32x4{0.f, 0.f, 0.f, 0.f});
     const int iy = y0 - 1 + r / C3X_PW, ix = x0 - 1 + r % C3X_PW;
     const bool in = r < C3X_NPIX && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
     const float4 bias2 = *(const float4*)(Bs + 64 + 4 * kq);
     float o[4] = {silu(acc[0] + bias2.x), silu(acc[1] + bias2.y), silu(acc[2] + bias2.z), silu(acc[3] + bias2.w)};
     if (!in) o[0] = o[1] = o[2] = o[3] = 0.f;
     bf16x4 h, m, l;
-    c3x_split4(o, h, m, l);
+    x3_split4(o, h, m, l);
     uint8_t* d = Up + r * C3X_UPB + 8 * kq;
     *(bf16x4*)d = h;
     *(bf16x4*)(d + 32) = m;
@@ -219,8 +172,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
       int tap = 2 * st + (kq >> 1);
       if (tap > 8) tap = 4;  // the tenth tap: zero weight columns, any valid pixel
       const uint8_t* s = Up + ((oy + tap / 3) * C3X_PW + ox + tap % 3) * C3X_UPB + 16 * (kq & 1);
-      acc = c3x_mfma32(w3h[st], w3m[st], w3l[st], *(const bf16x8*)s, *(const bf16x8*)(s + 32),
-                       *(const bf16x8*)(s + 64), acc);
+      acc = x3_mfma(w3h[st], w3m[st], w3l[st], *(const bf16x8*)s, *(const bf16x8*)(s + 32),
+                    *(const bf16x8*)(s + 64), acc);
     }
     uint8_t* d = Tp + ((oy + 1) * C3X_PW + ox + 1) * C3X_TPB + 8 * kq;
     const bf16x4 th = *(const bf16x4*)d, tm = *(const bf16x4*)(d + 64), tl = *(const bf16x4*)(d + 128);
@@ -230,7 +183,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
 #pragma unroll
     for (int j = 0; j < 4; ++j) o[j] = ((float)th[j] + (float)tm[j] + (float)tl[j]) + silu(acc[j] + bb[j]);
     bf16x4 h, m, l;
-    c3x_split4(o, h, m, l);
+    x3_split4(o, h, m, l);
     *(bf16x4*)d = h;
     *(bf16x4*)(d + 64) = m;
     *(bf16x4*)(d + 128) = l;
@@ -244,8 +197,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
     for (int i = 0; i < 4; ++i) {
       const int pr = wave + 4 * i, oy = pr >> 1, nt = pr & 1, ox = col;
       const uint8_t* s = Tp + ((oy + 1) * C3X_PW + ox + 1) * C3X_TPB + 16 * kq;
-      const f32x4 acc = c3x_mfma32(w4h[nt], w4m[nt], w4l[nt], *(const bf16x8*)s, *(const bf16x8*)(s + 64),
-                                   *(const bf16x8*)(s + 128), f32x4{0.f, 0.f, 0.f, 0.f});
+      const f32x4 acc = x3_mfma(w4h[nt], w4m[nt], w4l[nt], *(const bf16x8*)s, *(const bf16x8*)(s + 64),
+                                *(const bf16x8*)(s + 128), f32x4{0.f, 0.f, 0.f, 0.f});
       const int co = nt * 16 + 4 * kq;
       const float4 bias = *(const float4*)(Bs + 32 + co);
       *(float4*)(y + ((size_t)(y0 + oy) * p.W + x0 + ox) * p.ys + co) =

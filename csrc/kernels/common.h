@@ -18,6 +18,8 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));  // not HIP's uint4 struct: arrays of it stay in VGPRs
 
 namespace arena {
 
@@ -64,22 +66,6 @@ __device__ __forceinline__ uint2 pack4(const float* f) {
   return __builtin_bit_cast(uint2, v);
 }
 
-// Triple-bf16 split of two floats at once: v = h + m + l with h = bf16(v), m = bf16(v - h), l = bf16(v - h - m)
-// (the operand planes of the fp32-accurate MFMA kernels).  Bit-identical to the element-wise form
-//   th = (bf16)v; r = v - (float)th; tm = (bf16)r; l = (bf16)(r - (float)tm)
-// but 10 VALU per pair instead of 12-13: one v_cvt_pk_bf16_f32 converts both values, the packed word is widened
-// back with one shift (low half) and one mask (high half), and the residual is one v_pk_add_f32.
-__device__ __forceinline__ f32x2 widen_bf16x2(bf16x2 v) {
-  const unsigned u = __builtin_bit_cast(unsigned, v);
-  return f32x2{__builtin_bit_cast(float, u << 16), __builtin_bit_cast(float, u & 0xffff0000u)};
-}
-__device__ __forceinline__ void split_bf16x3_pair(f32x2 v, bf16x2& h, bf16x2& m, bf16x2& l) {
-  h = __builtin_convertvector(v, bf16x2);
-  const f32x2 r = v - widen_bf16x2(h);
-  m = __builtin_convertvector(r, bf16x2);
-  l = __builtin_convertvector(r - widen_bf16x2(m), bf16x2);
-}
-
 // 8 consecutive elements of an NHWC row as fp32, for kernels templated on the
 // activation type (bf16 pipeline / exact-fp32 pipeline).
 __device__ __forceinline__ void load8(const bf16* p, float* v) { unpack8(*(const uint4*)p, v); }
@@ -102,6 +88,10 @@ __device__ __forceinline__ void store8(float* p, const float* v) {
 __device__ __forceinline__ uint4 load16_or_zero(const void* p, const void* safe, bool ok) {
   const uint4 v = *(const uint4*)(ok ? p : safe);
   return ok ? v : make_uint4(0u, 0u, 0u, 0u);
+}
+__device__ __forceinline__ float4 load_f4_or_zero(const float* p, const float* safe, bool ok) {
+  const float4 v = *(const float4*)(ok ? p : safe);
+  return ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 __device__ __forceinline__ int live_batch(int cap, const int* bdev) {

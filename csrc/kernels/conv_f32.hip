@@ -29,26 +29,14 @@
 #include <stdexcept>
 #include <string>
 
-#include "common.h"
 #include "launch.h"
 #include "letterbox.h"
+#include "x3.h"
 
 namespace arena {
 
-__device__ __forceinline__ float4 load_f4_or_zero(const float* p, const float* safe, bool ok) {
-  const float4 v = *(const float4*)(ok ? p : safe);
-  return ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
 __device__ __forceinline__ float f4_get(const float4& v, int s) {
   return s == 0 ? v.x : s == 1 ? v.y : s == 2 ? v.z : v.w;
-}
-
-// Bijective XCD-aware block remap (8 XCDs, round-robin dispatch): consecutive
-// logical tiles land on the same XCD so neighbouring pixel tiles share its L2.
-__device__ __forceinline__ int xcd_remap(int bx, int nx) {
-  const int q = nx / 8, r = nx % 8, x = bx % 8, y = bx / 8;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + y;
 }
 
 template <int WC, int WP>
@@ -374,20 +362,10 @@ static void launch_lds(const ConvParams& p, hipStream_t s, long M) {
 }
 
 // ---------------------------------------------------------------------------
-// fp32-accurate implicit GEMM on the bf16 matrix cores ("x3": triple-bf16
-// split).  fp32 MFMA issues at 1/16 of the bf16 rate, so the fp32 kernels above
-// are matrix-core bound.  Every fp32 operand is split exactly into three bf16
-// terms, v = h + m + l (h = rn_bf16(v), m = rn_bf16(v - h), l = rn_bf16(v - h
-// - m); each residual is exact in fp32 and 3 x 8 significant bits cover fp32's
-// 24), and the product is formed from the six partial products whose order is
-// <= 2^-16 of |a||b|:
-//   a*b ~= ah*bh + ah*bm + am*bh + ah*bl + al*bh + am*bm
-// The dropped terms (am*bl, al*bm, al*bl) are below 2^-24 |a||b| — the size of
-// fp32's own product rounding — and bf16 products are exact in the fp32
-// accumulator, so the result has fp32-level error (tests/test_fp32_gpu.py
-// compares it to fp64 next to the exact-fp32 kernel).  Six 16x16x32 bf16 MFMAs
-// (16 cycles each) replace eight 16x16x4 fp32 MFMAs (32 cycles each) per 32-deep
-// k chunk: 2.7x less matrix-core time.
+// fp32-accurate implicit GEMM on the bf16 matrix cores: the x3 scheme (x3.h).  fp32 MFMA issues at 1/16 of
+// the bf16 rate, so the fp32 kernels above are matrix-core bound; tests/test_fp32_gpu.py compares the x3 result
+// to fp64 next to the exact-fp32 kernel.  Six 16x16x32 bf16 MFMAs (16 cycles each) replace eight 16x16x4 fp32
+// MFMAs (32 cycles each) per 32-deep k chunk: 2.7x less matrix-core time.
 //
 // Staging is the fp32 LDS kernel's (float4 of 4 consecutive k per thread, same
 // fp32 weight blob), split on the way into LDS: a row holds the chunk's 32 k as
@@ -398,20 +376,18 @@ static void launch_lds(const ConvParams& p, hipStream_t s, long M) {
 constexpr int X3_KC = 32;
 constexpr int X3_PITCH = 3 * X3_KC + 16;  // bf16 per LDS row: 14 slots = 2 (mod 4), conflict-free b128 reads
 
-__device__ __forceinline__ void split3(float v, bf16& h, bf16& m, bf16& l) {
-  h = (bf16)v;
-  const float r = v - (float)h;
-  m = (bf16)r;
-  l = (bf16)(r - (float)m);
+// x3_split of a float4's four values (by value: through a reference the staging loops compile differently)
+__device__ __forceinline__ void split_f4(const float4 v, bf16x4& h, bf16x4& m, bf16x4& l) {
+  bf16 th, tm, tl;
+  x3_split(v.x, th, tm, tl); h[0] = th; m[0] = tm; l[0] = tl;
+  x3_split(v.y, th, tm, tl); h[1] = th; m[1] = tm; l[1] = tl;
+  x3_split(v.z, th, tm, tl); h[2] = th; m[2] = tm; l[2] = tl;
+  x3_split(v.w, th, tm, tl); h[3] = th; m[3] = tm; l[3] = tl;
 }
 
 __device__ __forceinline__ void store_split4(bf16* row, int k, const float4& v) {
   bf16x4 h, m, l;
-  bf16 th, tm, tl;
-  split3(v.x, th, tm, tl); h[0] = th; m[0] = tm; l[0] = tl;
-  split3(v.y, th, tm, tl); h[1] = th; m[1] = tm; l[1] = tl;
-  split3(v.z, th, tm, tl); h[2] = th; m[2] = tm; l[2] = tl;
-  split3(v.w, th, tm, tl); h[3] = th; m[3] = tm; l[3] = tl;
+  split_f4(v, h, m, l);
   *(bf16x4*)(row + k) = h;
   *(bf16x4*)(row + X3_KC + k) = m;
   *(bf16x4*)(row + 2 * X3_KC + k) = l;
@@ -522,16 +498,7 @@ __global__ __launch_bounds__(256) void conv_x3_lds_kernel(const ConvParams p) {
       const bf16x8 bm = *(const bf16x8*)(r + X3_KC);
       const bf16x8 bl = *(const bf16x8*)(r + 2 * X3_KC);
 #pragma unroll
-      for (int j = 0; j < NF; ++j) {
-        // smallest terms first: they are added while the accumulator is smallest
-        f32x4 c = acc[f][j];
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[j], bm, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[j], bh, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[j], bl, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[j], bh, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[j], bm, c, 0, 0, 0);
-        acc[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[j], bh, c, 0, 0, 0);
-      }
+      for (int j = 0; j < NF; ++j) acc[f][j] = x3_mfma(ah[j], am[j], al[j], bh, bm, bl, acc[f][j]);
     }
     if (kc + 1 < nk) sstore(cur ^ 1);
     __syncthreads();
@@ -798,7 +765,7 @@ static bool launch_halo_n(const ConvParams& p, hipStream_t s) {
 
 // ---------------------------------------------------------------------------
 // 3x3 stride-1 halo tiles on the bf16 matrix cores with the triple-bf16 split
-// (x3, see conv_x3_lds_kernel): the large detect-head / neck 3x3 convs are the
+// (x3.h): the large detect-head / neck 3x3 convs are the
 // one place the fp32 kernels are matrix-core bound (50-65 % MFMA busy,
 // profiles/r2_fp32_pmc_ops.md), and here each staged input element feeds nine
 // taps, so splitting it on the way into LDS costs 1/9 per use.
@@ -929,15 +896,7 @@ __global__ __launch_bounds__(X3H_TH * 32) void conv_x3_halo_kernel(const ConvPar
         const bf16x8 bm = *(const bf16x8*)(r + 32);
         const bf16x8 bl = *(const bf16x8*)(r + 64);
 #pragma unroll
-        for (int j = 0; j < NF; ++j) {
-          f32x4 c = acc[f][j];
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[j], bm, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[j], bh, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[j], bl, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[j], bh, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[j], bm, c, 0, 0, 0);
-          acc[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[j], bh, c, 0, 0, 0);
-        }
+        for (int j = 0; j < NF; ++j) acc[f][j] = x3_mfma(ah[j], am[j], al[j], bh, bm, bl, acc[f][j]);
       }
     }
     __syncthreads();
@@ -1060,11 +1019,7 @@ __global__ __launch_bounds__(256) void conv_x3_h16_kernel(const ConvParams p) {
     const bool ok = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
     const float4 v = load_f4_or_zero(x + ((size_t)iy * p.W + ix) * p.xs + 4 * g, x, ok);
     bf16x4 h, m, l;
-    bf16 th, tm, tl;
-    split3(v.x, th, tm, tl); h[0] = th; m[0] = tm; l[0] = tl;
-    split3(v.y, th, tm, tl); h[1] = th; m[1] = tm; l[1] = tl;
-    split3(v.z, th, tm, tl); h[2] = th; m[2] = tm; l[2] = tl;
-    split3(v.w, th, tm, tl); h[3] = th; m[3] = tm; l[3] = tl;
+    split_f4(v, h, m, l);
     bf16* d = &sX[px * H16_XP + 4 * g];
     *(bf16x4*)d = h;
     *(bf16x4*)(d + 16) = m;
@@ -1080,11 +1035,7 @@ __global__ __launch_bounds__(256) void conv_x3_h16_kernel(const ConvParams p) {
     float4 v = load_f4_or_zero(w + (size_t)n * p.Kpad + k, w, ok);
     if constexpr (LB) v = make_float4(v.x / 255.0f, v.y / 255.0f, v.z / 255.0f, v.w / 255.0f);
     bf16x4 h, m, l;
-    bf16 th, tm, tl;
-    split3(v.x, th, tm, tl); h[0] = th; m[0] = tm; l[0] = tl;
-    split3(v.y, th, tm, tl); h[1] = th; m[1] = tm; l[1] = tl;
-    split3(v.z, th, tm, tl); h[2] = th; m[2] = tm; l[2] = tl;
-    split3(v.w, th, tm, tl); h[3] = th; m[3] = tm; l[3] = tl;
+    split_f4(v, h, m, l);
     const int slab = q >> 3, kk = 4 * (q & 7);
     bf16* d = &sW[(row * 3 + ky) * H16_WPK + slab * 96 + kk];
     *(bf16x4*)d = h;
@@ -1119,25 +1070,12 @@ __global__ __launch_bounds__(256) void conv_x3_h16_kernel(const ConvParams p) {
         if constexpr (LB) {  // exact integer activations: one plane
           const bf16x8 bh = *(const bf16x8*)r;
 #pragma unroll
-          for (int j = 0; j < NF; ++j) {
-            f32x4 c = acc[f][j];
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[j], bh, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[j], bh, c, 0, 0, 0);
-            acc[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[j], bh, c, 0, 0, 0);
-          }
+          for (int j = 0; j < NF; ++j) acc[f][j] = x3_mfma_b1(ah[j], am[j], al[j], bh, acc[f][j]);
           continue;
         }
         const bf16x8 bh = *(const bf16x8*)r, bm = *(const bf16x8*)(r + 16), bl = *(const bf16x8*)(r + 32);
 #pragma unroll
-        for (int j = 0; j < NF; ++j) {
-          f32x4 c = acc[f][j];
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[j], bm, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[j], bh, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[j], bl, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[j], bh, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[j], bm, c, 0, 0, 0);
-          acc[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[j], bh, c, 0, 0, 0);
-        }
+        for (int j = 0; j < NF; ++j) acc[f][j] = x3_mfma(ah[j], am[j], al[j], bh, bm, bl, acc[f][j]);
       }
     }
   }
@@ -1262,16 +1200,6 @@ static bool halo_f32(const ConvParams& p, hipStream_t s, bool force = false) {
 // from LDS (row pitch 6K + 32 B = 2 (mod 4) 16-B slots: conflict-free ds_read_b128).
 constexpr int STR_THREADS = 256;
 
-__device__ __forceinline__ f32x4 mfma_x3f(const bf16x8& ah, const bf16x8& am, const bf16x8& al, const bf16x8& bh,
-                                          const bf16x8& bm, const bf16x8& bl, f32x4 c) {
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bm, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bm, c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
-}
-
 template <int NF, int KS>
 __global__ __launch_bounds__(STR_THREADS) void conv_x3_stream_kernel(const ConvParams p) {
   constexpr int BN = NF * 16, K = KS * 32, WP = 6 * K + 32;
@@ -1293,11 +1221,7 @@ __global__ __launch_bounds__(STR_THREADS) void conv_x3_stream_kernel(const ConvP
     float4 v = *(const float4*)(ok ? w + (size_t)(n0 + row) * p.Kpad + k : w);
     if (!ok) v = make_float4(0.f, 0.f, 0.f, 0.f);
     bf16x4 h, m, l;
-    bf16 th, tm, tl;
-    split3(v.x, th, tm, tl); h[0] = th; m[0] = tm; l[0] = tl;
-    split3(v.y, th, tm, tl); h[1] = th; m[1] = tm; l[1] = tl;
-    split3(v.z, th, tm, tl); h[2] = th; m[2] = tm; l[2] = tl;
-    split3(v.w, th, tm, tl); h[3] = th; m[3] = tm; l[3] = tl;
+    split_f4(v, h, m, l);
     uint8_t* r = sW + row * WP + k * 2;
     *(bf16x4*)r = h;
     *(bf16x4*)(r + 2 * K) = m;
@@ -1357,7 +1281,7 @@ __global__ __launch_bounds__(STR_THREADS) void conv_x3_stream_kernel(const ConvP
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         bf16 th, tm, tl;
-        split3(v[i], th, tm, tl);
+        x3_split(v[i], th, tm, tl);
         bh[i] = th;
         bm[i] = tm;
         bl[i] = tl;
@@ -1365,8 +1289,8 @@ __global__ __launch_bounds__(STR_THREADS) void conv_x3_stream_kernel(const ConvP
 #pragma unroll
       for (int j = 0; j < NF; ++j) {
         const uint8_t* ra = sW + (j * 16 + col) * WP + sl * 64 + kq * 16;
-        acc[j] = mfma_x3f(*(const bf16x8*)ra, *(const bf16x8*)(ra + 2 * K), *(const bf16x8*)(ra + 4 * K), bh, bm,
-                          bl, acc[j]);
+        acc[j] = x3_mfma(*(const bf16x8*)ra, *(const bf16x8*)(ra + 2 * K), *(const bf16x8*)(ra + 4 * K), bh, bm,
+                         bl, acc[j]);
       }
     }
     const int pix = t * 16 + col;

@@ -20,10 +20,6 @@ namespace {
 __device__ __forceinline__ float f4_get(const float4& v, int s) {
   return s == 0 ? v.x : s == 1 ? v.y : s == 2 ? v.z : v.w;
 }
-__device__ __forceinline__ float4 load_f4_or_zero(const float* p, const float* safe, bool ok) {
-  const float4 v = *(const float4*)(ok ? p : safe);
-  return ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-}
 }  // namespace
 }  // namespace arena
 

@@ -12,12 +12,10 @@
 //   * weights are split once, at plan time (engine/planner.py pack_conv_weight_x3),
 //     into [K/32][Cout_pad][h 32 | m 32 | l 32] bf16 and staged by plain copies;
 //   * activations are split once per staged element (8 consecutive k per item,
-//     v = h + m + l exactly, see conv_x3_lds_kernel) and each staged row feeds
-//     BN / 32 MFMA tiles;
+//     the split of x3.h) and each staged row feeds BN / 32 MFMA tiles;
 //   * the matrix op is v_mfma_f32_32x32x16_bf16: 32 cycles, 24 of them free for
 //     vector issue, and half the LDS fragment reads per FLOP of the 16x16 form;
-//   * six partial products per operand pair (the dropped am*bl, al*bm, al*bl are
-//     below 2^-24 |a||b|), smallest first, fp32 accumulation;
+//   * the six-product chain of x3.h per operand pair;
 //   * LDS rows of 208 B (13 16-B slots, odd): the fragment reads (lane l: row
 //     l & 31, k-half l >> 5) put 16 distinct rows in each ds_read_b128 lane
 //     group on 16 distinct slots; the stage is double-buffered (one barrier per
@@ -31,57 +29,16 @@
 #include <stdexcept>
 #include <string>
 
-#include "common.h"
 #include "launch.h"
+#include "x3.h"
 
 namespace arena {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));  // not HIP's uint4 struct: arrays of it stay in VGPRs
-
 constexpr int XG_PITCH = 104;  // bf16 per LDS row: 3 planes x 32 k + 8 pad (208 B = 13 slots)
 
 __host__ __device__ constexpr int xg_lds_bytes(int BM, int BN) { return 2 * (BM + BN) * XG_PITCH * 2; }
-
-__device__ __forceinline__ int xg_xcd_remap(int bx, int nx) {
-  const int q = nx / 8, r = nx % 8, x = bx % 8, y = bx / 8;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + y;
-}
-
-__device__ __forceinline__ f32x4 xg_load_f4(const float* p, const float* safe, bool ok) {
-  const f32x4 v = *(const f32x4*)(ok ? p : safe);
-  return ok ? v : f32x4{0.f, 0.f, 0.f, 0.f};
-}
-
-__device__ __forceinline__ u32x4 xg_load_u4(const bf16* p, const bf16* safe, bool ok) {
-  const u32x4 v = *(const u32x4*)(ok ? p : safe);
-  return ok ? v : u32x4{0u, 0u, 0u, 0u};
-}
-
-__device__ __forceinline__ void xg_split8(const f32x4 a, const f32x4 b, bf16x8& h, bf16x8& m, bf16x8& l) {
-  const float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const bf16 th = (bf16)v[i];
-    const float r = v[i] - (float)th;
-    const bf16 tm = (bf16)r;
-    h[i] = th;
-    m[i] = tm;
-    l[i] = (bf16)(r - (float)tm);
-  }
-}
-
-__device__ __forceinline__ f32x16 xg_mfma_x3(const bf16x8& ah, const bf16x8& am, const bf16x8& al,
-                                             const bf16x8& bh, const bf16x8& bm, const bf16x8& bl, f32x16 c) {
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, c, 0, 0, 0);
-}
 
 }  // namespace
 
@@ -110,7 +67,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_x3g_kernel(const ConvParams
   const int nsplit = SK ? p.sk_splits : 1;
   const int ntiles = (int)gridDim.x / nsplit;
   const int split = SK ? (int)blockIdx.x / ntiles : 0;
-  const int bx = xg_xcd_remap((int)blockIdx.x - split * ntiles, ntiles);
+  const int bx = xcd_remap((int)blockIdx.x - split * ntiles, ntiles);
   const int mt = bx / ntn, nt = bx - mt * ntn;
   const int m0 = mt * BM, n0 = nt * BN;
   if (m0 >= M) return;
@@ -200,7 +157,9 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_x3g_kernel(const ConvParams
     for (int j = 0; j < AI; ++j) {
       const int i = tid + NT * j;
       bf16x8 h, m, l;
-      xg_split8(ra[j][0], ra[j][1], h, m, l);
+      const float v[8] = {ra[j][0][0], ra[j][0][1], ra[j][0][2], ra[j][0][3],
+                          ra[j][1][0], ra[j][1][1], ra[j][1][2], ra[j][1][3]};
+      x3_split8(v, h, m, l);
       bf16* d = a + (i >> 2) * XG_PITCH + 8 * (i & 3);
       *(bf16x8*)d = h;
       *(bf16x8*)(d + 32) = m;
@@ -243,7 +202,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_x3g_kernel(const ConvParams
         const bf16* r = a + ((wm * TM + tm) * 32 + fr) * XG_PITCH + ks * 16 + fk;
         const bf16x8 xh = *(const bf16x8*)r, xm = *(const bf16x8*)(r + 32), xl = *(const bf16x8*)(r + 64);
 #pragma unroll
-        for (int tn = 0; tn < TN; ++tn) acc[tm][tn] = xg_mfma_x3(wh[tn], wmid[tn], wl[tn], xh, xm, xl, acc[tm][tn]);
+        for (int tn = 0; tn < TN; ++tn) acc[tm][tn] = x3_mfma(wh[tn], wmid[tn], wl[tn], xh, xm, xl, acc[tm][tn]);
       }
     }
   };

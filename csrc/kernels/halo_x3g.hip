@@ -20,9 +20,7 @@
 //   * 32x32x16 fragments read half the LDS bytes per MAC of the 16x16x32 form, and every wave holds TM
 //     pixel fragments: per tap a wave reads TM + TN fragment triples for 6 TM TN MFMAs.
 //
-// Six partial products per operand pair (am*bm, al*bh, ah*bl, am*bh, ah*bm, ah*bh, smallest first; the
-// dropped am*bl, al*bm, al*bl are below 2^-24 |a||b|), fp32 accumulation: the error bound of the other
-// fp32-accurate kernels (tests/test_fp32_gpu.py).
+// The six-product chain of x3.h: the error bound of the other fp32-accurate kernels (tests/test_fp32_gpu.py).
 //
 // Workgroup: WM x WN waves.  Output tile TH x TW pixels of one image x BN channels; a pixel fragment is
 // 32 pixels = (32 / TW) rows x TW columns, wave (wm, wn) computes pixel fragments wm*TM .. +TM-1 and
@@ -33,15 +31,12 @@
 #include <stdexcept>
 #include <string>
 
-#include "common.h"
 #include "launch.h"
+#include "x3.h"
 
 namespace arena {
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int HG_P = 56;  // bf16 per LDS row: 3 planes x 16 k + 8 pad (112 B)
 constexpr int HG_GATE_MAX_N = 80;  // gating channels per pixel at most (ConvParams.gate_n): the Detect head's classes
@@ -52,21 +47,6 @@ __host__ __device__ constexpr int hg_lds_bytes(int TW, int WM, int WN, int TM, i
 }
 __host__ __device__ constexpr int hr_lds_bytes(int TW, int WM, int TM) {  // x3hr: the halo only
   return (hg_th(TW, WM, TM) + 2) * (TW + 2) * HG_P * 2;
-}
-
-__device__ __forceinline__ int hg_xcd_remap(int bx, int nx) {
-  const int q = nx / 8, r = nx % 8, x = bx % 8, y = bx / 8;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + y;
-}
-
-__device__ __forceinline__ f32x16 hg_mfma_x3(const bf16x8& ah, const bf16x8& am, const bf16x8& al,
-                                             const bf16x8& bh, const bf16x8& bm, const bf16x8& bl, f32x16 c) {
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, c, 0, 0, 0);
 }
 
 }  // namespace
@@ -102,14 +82,7 @@ __device__ __forceinline__ void hg_epilogue(const ConvParams& p, f32x16 (&acc)[T
           }
           const int ks = 2 * tn + sh;
 #pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const bf16 th = (bf16)v[e];
-            const float r = v[e] - (float)th;
-            const bf16 tmid = (bf16)r;
-            bh[ks][e] = th;
-            bm[ks][e] = tmid;
-            bl[ks][e] = (bf16)(r - (float)tmid);
-          }
+          for (int e = 0; e < 8; ++e) x3_split_at(v[e], e, bh[ks], bm[ks], bl[ks]);
         }
       const int r = (wm * TM + tm) * RF + fr / TW, c = fr % TW;
       const int oy = oy0 + r, ox = ox0 + c;
@@ -126,7 +99,7 @@ __device__ __forceinline__ void hg_epilogue(const ConvParams& p, f32x16 (&acc)[T
           const bf16x8 wh = *(const bf16x8*)(wrow + 16 * ks);
           const bf16x8 wmid = *(const bf16x8*)(wrow + K2 + 16 * ks);
           const bf16x8 wl = *(const bf16x8*)(wrow + 2 * K2 + 16 * ks);
-          a2 = hg_mfma_x3(wh, wmid, wl, bh[ks], bm[ks], bl[ks], a2);
+          a2 = x3_mfma(wh, wmid, wl, bh[ks], bm[ks], bl[ks], a2);
         }
         if (!live) continue;
 #pragma unroll
@@ -206,7 +179,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_x3hg_kernel(const ConvParam
   const int tiles_x = (p.Wo + TW - 1) / TW, tiles_y = (p.Ho + TH - 1) / TH;
   const int ntn = (p.Cout_pad + BN - 1) / BN;
   const int per_img = tiles_x * tiles_y * ntn;
-  const int bx = hg_xcd_remap(blockIdx.x, gridDim.x);
+  const int bx = xcd_remap(blockIdx.x, gridDim.x);
   const int b = bx / per_img;
   if (b >= live_batch(p.B, p.bdev)) return;
   int t = bx - b * per_img;
@@ -290,7 +263,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_x3hg_kernel(const ConvParam
     for (int j = 0; j < XI; ++j) {
       const int i = tid + NT * j;
       if (HPIX * 4 % NT == 0 || i < HPIX * 4) {
-        bf16x2 h0, m0, l0, h1, m1, l1;  // split two values at a time (common.h)
+        bf16x2 h0, m0, l0, h1, m1, l1;  // split two values at a time (x3.h)
         split_bf16x3_pair(f32x2{rx[j][0], rx[j][1]}, h0, m0, l0);
         split_bf16x3_pair(f32x2{rx[j][2], rx[j][3]}, h1, m1, l1);
         bf16* d = sX + (i >> 2) * HG_P + 4 * (i & 3);
@@ -351,7 +324,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_x3hg_kernel(const ConvParam
       const bf16* r = wb + ((wn * TN + tn) * 32 + fr) * HG_P + fk;
       const bf16x8 wh = *(const bf16x8*)r, wmid = *(const bf16x8*)(r + 16), wl = *(const bf16x8*)(r + 32);
 #pragma unroll
-      for (int tm = 0; tm < TM; ++tm) acc[tm][tn] = hg_mfma_x3(wh, wmid, wl, xh[tm], xm[tm], xl[tm], acc[tm][tn]);
+      for (int tm = 0; tm < TM; ++tm) acc[tm][tn] = x3_mfma(wh, wmid, wl, xh[tm], xm[tm], xl[tm], acc[tm][tn]);
     }
   };
 
@@ -408,7 +381,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_x3hr_kernel(const ConvParam
   const int tiles_x = (p.Wo + TW - 1) / TW, tiles_y = (p.Ho + TH - 1) / TH;
   const int ntn = (p.Cout_pad + BN - 1) / BN;
   const int per_img = tiles_x * tiles_y * ntn;
-  const int bx = hg_xcd_remap(blockIdx.x, gridDim.x);
+  const int bx = xcd_remap(blockIdx.x, gridDim.x);
   const int b = bx / per_img;
   if (b >= live_batch(p.B, p.bdev)) return;
   int t = bx - b * per_img;
@@ -466,15 +439,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_x3hr_kernel(const ConvParam
       if (HPIX * 4 % NT == 0 || i < HPIX * 4) {
         bf16x4 h, m, l;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float v = rx[j][e];
-          const bf16 th = (bf16)v;
-          const float r = v - (float)th;
-          const bf16 tm = (bf16)r;
-          h[e] = th;
-          m[e] = tm;
-          l[e] = (bf16)(r - (float)tm);
-        }
+        for (int e = 0; e < 4; ++e) x3_split_at(rx[j][e], e, h, m, l);
         bf16* d = sX + (i >> 2) * HG_P + 4 * (i & 3);
         *(bf16x4*)d = h;
         *(bf16x4*)(d + 16) = m;
@@ -523,7 +488,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_x3hr_kernel(const ConvParam
       const bf16x8 wh = __builtin_bit_cast(bf16x8, w[tn][0]), wmid = __builtin_bit_cast(bf16x8, w[tn][1]),
                    wl = __builtin_bit_cast(bf16x8, w[tn][2]);
 #pragma unroll
-      for (int tm = 0; tm < TM; ++tm) acc[tm][tn] = hg_mfma_x3(wh, wmid, wl, xh[tm], xm[tm], xl[tm], acc[tm][tn]);
+      for (int tm = 0; tm < TM; ++tm) acc[tm][tn] = x3_mfma(wh, wmid, wl, xh[tm], xm[tm], xl[tm], acc[tm][tn]);
     }
   };
 

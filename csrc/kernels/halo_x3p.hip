@@ -2,8 +2,8 @@
 //
 // conv_x3_halo_kernel (conv_f32.hip) with its weight staging replaced: the same output tile (TH rows x 16
 // columns of one image x BN = NF*16 channels, wave w computing rows w and w + TH/2), the same 32-channel input
-// chunks, the same K order (chunk, ky, kx) and the same six products per 32-deep step (am*bm, al*bh, ah*bl,
-// am*bh, ah*bm, ah*bh), so every output is bit-identical to impl 101 / 102 / 103 / 108 / 109 whatever the tile.
+// chunks, the same K order (chunk, ky, kx) and the same six products per 32-deep step (x3.h), so every output
+// is bit-identical to impl 101 / 102 / 103 / 108 / 109 whatever the tile.
 // What differs is how a stage reaches LDS:
 //
 //   * weights are the plan's pre-split bf16 planes (ConvParams.w3, engine/planner.py pack_conv_weight_x3:
@@ -13,7 +13,7 @@
 //     two subtracts per element: ~70 % of its staging work at NF 3).  Per-thread piece offsets are computed
 //     once; a stage adds one wave-uniform offset (raw buffer loads, rows past Cout_pad read zeros);
 //   * the input halo's per-thread offsets are computed once per kernel as well, and the chunk is split two
-//     values at a time (split_bf16x3_pair, common.h);
+//     values at a time (split_bf16x3_pair, x3.h);
 //   * TS = taps per weight stage: 3 stages one kernel row (ky) as the old kernel does (608-B rows); 1 stages a
 //     single tap (224-B rows), which lets one workgroup hold all nine 16-channel fragments of the 144-channel
 //     Detect-head convs (NF 9: 32 KB of weights per stage) so that their halo is staged and split once, not
@@ -45,25 +45,18 @@
 #include <string>
 
 #include "../runtime/head_marks.h"
-#include "common.h"
 #include "launch.h"
+#include "x3.h"
 
 namespace arena {
 
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int HP_TW = 16, HP_HC = HP_TW + 2;
 constexpr int HP_XP = 3 * 32 + 16;  // bf16 per halo pixel (224 B)
 __host__ __device__ constexpr int hp_wp(int TS) { return TS * 96 + 16; }  // bf16 per weight row of one stage
 __host__ __device__ constexpr int hp_lds_bytes(int NF, int TH, int TS) {
   return ((TH + 2) * HP_HC * HP_XP + NF * 16 * hp_wp(TS)) * 2;
-}
-
-__device__ __forceinline__ int hp_xcd_remap(int bx, int nx) {
-  const int q = nx / 8, r = nx % 8, x = bx % 8, y = bx / 8;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + y;
 }
 
 }  // namespace
@@ -87,7 +80,7 @@ __global__ __launch_bounds__(TH * 32) void conv_x3hp_kernel(const ConvParams p) 
   const int col = lane & 15, kq = lane >> 4;
   const int tiles_x = (p.Wo + HP_TW - 1) / HP_TW, tiles_y = (p.Ho + TH - 1) / TH;
   const int tiles = tiles_x * tiles_y;
-  const int bx = hp_xcd_remap(blockIdx.x, gridDim.x);
+  const int bx = xcd_remap(blockIdx.x, gridDim.x);
   const int b = bx / tiles;
   if (b >= live_batch(p.B, p.bdev)) return;
   const int t = bx - b * tiles;
@@ -153,7 +146,7 @@ __global__ __launch_bounds__(TH * 32) void conv_x3hp_kernel(const ConvParams p) 
     for (int j = 0; j < XI; ++j) {
       const int i = tid + NT * j;
       if (HPIX * 8 % NT == 0 || i < HPIX * 8) {
-        bf16x2 h0, m0, l0, h1, m1, l1;
+        bf16x2 h0, m0, l0, h1, m1, l1;  // split two values at a time (x3.h)
         split_bf16x3_pair(f32x2{rx[j][0], rx[j][1]}, h0, m0, l0);
         split_bf16x3_pair(f32x2{rx[j][2], rx[j][3]}, h1, m1, l1);
         bf16* d = sX + (i >> 3) * HP_XP + 4 * (i & 7);
@@ -213,15 +206,7 @@ __global__ __launch_bounds__(TH * 32) void conv_x3hp_kernel(const ConvParams p) 
         const bf16x8 am = *(const bf16x8*)(r + 32);
         const bf16x8 al = *(const bf16x8*)(r + 64);
 #pragma unroll
-        for (int f = 0; f < MF; ++f) {
-          f32x4 c = acc[f][j];
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bm[f], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[f], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[f], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bh[f], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bm[f], c, 0, 0, 0);
-          acc[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[f], c, 0, 0, 0);
-        }
+        for (int f = 0; f < MF; ++f) acc[f][j] = x3_mfma(ah, am, al, bh[f], bm[f], bl[f], acc[f][j]);
       }
     }
     __syncthreads();

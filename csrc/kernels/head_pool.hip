@@ -26,8 +26,8 @@
 #include <stdexcept>
 #include <string>
 
-#include "common.h"
 #include "launch.h"
+#include "x3.h"
 
 namespace arena {
 
@@ -132,7 +132,7 @@ void head_pool(const HeadPoolParams& p, hipStream_t s) {
 
 // ---------------------------------------------------------------------------
 // fp32 programs: the same fusion at fp32 accuracy on the bf16 matrix cores (triple-bf16 split, six partial
-// products per MFMA step, conv_f32.hip).  Unfused, the fp32 head was a 1x1 conv writing the 7x7x1280 fp32 map
+// products per MFMA step: x3.h).  Unfused, the fp32 head was a 1x1 conv writing the 7x7x1280 fp32 map
 // (251 KB per crop) plus an avgpool kernel reading it back: 73 + 17 us for 128 crops
 // (profiles/r2_fp32_stream2_ops.md ops 109-110).  The crop's pixels are split into [h|m|l] bf16 planes in LDS
 // once (64 rows x 1952 B: a pitch of 2 (mod 4) 16-B slots); each wave splits its weight fragments in
@@ -189,13 +189,7 @@ __global__ __launch_bounds__(kHeadF32Threads) void head_pool_f32_kernel(const He
       if (!ok) v = make_float4(0.f, 0.f, 0.f, 0.f);
       const float f[4] = {v.x, v.y, v.z, v.w};
       bf16x4 hh, m, l;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        hh[j] = (bf16)f[j];
-        const float r = f[j] - (float)hh[j];
-        m[j] = (bf16)r;
-        l[j] = (bf16)(r - (float)m[j]);
-      }
+      x3_split4(f, hh, m, l);
       uint8_t* d = xsf + px * PITCH + c * 8;
       *(bf16x4*)d = hh;
       *(bf16x4*)(d + 2 * KH) = m;
@@ -220,13 +214,7 @@ __global__ __launch_bounds__(kHeadF32Threads) void head_pool_f32_kernel(const He
 #pragma unroll
       for (int f = 0; f < kNF; ++f) {
         const float v[8] = {wr[f][0].x, wr[f][0].y, wr[f][0].z, wr[f][0].w, wr[f][1].x, wr[f][1].y, wr[f][1].z, wr[f][1].w};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          ah[f][j] = (bf16)v[j];
-          const float r = v[j] - (float)ah[f][j];
-          am[f][j] = (bf16)r;
-          al[f][j] = (bf16)(r - (float)am[f][j]);
-        }
+        x3_split8(v, ah[f], am[f], al[f]);
       }
       if (s + 1 < KSLABS) load_w(s + 1);  // next slab's weights in flight during this slab's MFMAs
 #pragma unroll
@@ -234,7 +222,7 @@ __global__ __launch_bounds__(kHeadF32Threads) void head_pool_f32_kernel(const He
         const uint8_t* r = xsf + (mm * 16 + row) * PITCH + (s - h * SH) * 64 + kq * 16;
         const bf16x8 bh = *(const bf16x8*)r, bm = *(const bf16x8*)(r + 2 * KH), bl = *(const bf16x8*)(r + 4 * KH);
 #pragma unroll
-        for (int f = 0; f < kNF; ++f) {
+        for (int f = 0; f < kNF; ++f) {  // x3_mfma (x3.h) by hand: through the call this loop is scheduled differently
           f32x4 c = acc[f][mm];
           c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[f], bm, c, 0, 0, 0);
           c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[f], bh, c, 0, 0, 0);

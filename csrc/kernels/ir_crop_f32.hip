@@ -43,42 +43,17 @@
 #include <stdexcept>
 #include <string>
 
-#include "common.h"
 #include "launch.h"
+#include "x3.h"
 
 namespace arena {
 
 namespace {
 
 constexpr int IRX_THREADS = 512, IRX_WAVES = IRX_THREADS / 64;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int imin(int a, int b) { return a < b ? a : b; }
 constexpr int imax(int a, int b) { return a > b ? a : b; }
-
-// 8 fp32 -> three bf16x8 planes with v = h + m + l (round to nearest even at each step)
-__device__ __forceinline__ void split8(const float* v, bf16x8& h, bf16x8& m, bf16x8& l) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const bf16 th = (bf16)v[i];
-    const float r = v[i] - (float)th;
-    const bf16 tm = (bf16)r;
-    h[i] = th;
-    m[i] = tm;
-    l[i] = (bf16)(r - (float)tm);
-  }
-}
-
-// a*b to fp32 accuracy from the split planes; smallest terms first (added while the sum is smallest)
-__device__ __forceinline__ f32x4 mfma_x3(const bf16x8& ah, const bf16x8& am, const bf16x8& al, const bf16x8& bh,
-                                         const bf16x8& bm, const bf16x8& bl, f32x4 c) {
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bm, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bm, c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
-}
 
 }  // namespace
 
@@ -238,7 +213,7 @@ __global__ __launch_bounds__(IRX_THREADS) void ir_x3_kernel(const IrParams p) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) v[i] = 0.f;
       }
-      split8(v, xh[ks], xm[ks], xl[ks]);
+      x3_split8(v, xh[ks], xm[ks], xl[ks]);
     }
     if (ok) e_off = ((iy - iy0) * EW + ix + 1) * 32;
   }
@@ -273,7 +248,7 @@ __global__ __launch_bounds__(IRX_THREADS) void ir_x3_kernel(const IrParams p) {
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
           const uint8_t* ra = WEs + (ht * 16 + col) * G::WEB + (ks * 32 + 8 * kq) * 2;
-          e = mfma_x3(*(const bf16x8*)ra, *(const bf16x8*)(ra + INP * 2), *(const bf16x8*)(ra + INP * 4), xh[ks],
+          e = x3_mfma(*(const bf16x8*)ra, *(const bf16x8*)(ra + INP * 2), *(const bf16x8*)(ra + INP * 4), xh[ks],
                       xm[ks], xl[ks], e);
         }
         if (e_off >= 0) {
@@ -322,13 +297,13 @@ __global__ __launch_bounds__(IRX_THREADS) void ir_x3_kernel(const IrParams p) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) a[i] = relu6f(a[i]);
         bf16x8 dh, dm, dl;
-        split8(a, dh, dm, dl);
+        x3_split8(a, dh, dm, dl);
 #pragma unroll
         for (int j = 0; j < G::OTG; ++j) {
           const int ot = ot0 + j;
           if (ot >= NOT) break;
           const uint8_t* ra = WPs + (ot * 16 + col) * G::WPB + (ks * 32 + 8 * kq) * 2;
-          acc[j] = mfma_x3(*(const bf16x8*)ra, *(const bf16x8*)(ra + HC * 2), *(const bf16x8*)(ra + HC * 4), dh, dm,
+          acc[j] = x3_mfma(*(const bf16x8*)ra, *(const bf16x8*)(ra + HC * 2), *(const bf16x8*)(ra + HC * 4), dh, dm,
                            dl, acc[j]);
         }
       }

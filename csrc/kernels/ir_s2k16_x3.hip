@@ -12,7 +12,7 @@
 //     triple-bf16 split pair up along K: with A = [p | q] and B = [r | s] (16-wide halves) one
 //     v_mfma_f32_16x16x32_bf16 yields p.r + q.s, so
 //         [am | al].[bm | bh],  [ah | am].[bl | bh],  [ah | ah].[bm | bh]
-//     are the six terms of itx_mfma, smallest first, in three MFMAs.  A lane's 8-element fragment covers k = 8 kq
+//     are the six terms of x3_mfma (x3.h), smallest first, in three MFMAs.  A lane's 8-element fragment covers k = 8 kq
 //     .. + 7 of the 32, so the packing is only a choice of plane per lane: lanes kq < 2 take the first plane of each
 //     pair, lanes kq >= 2 the second, both for channels 8 (kq & 1) .. + 7.
 //   * The input halo is loaded and split once per workgroup, into bf16 planes in the LDS region that later holds E;
@@ -28,7 +28,6 @@
 #include <cstdlib>
 #include <stdexcept>
 
-#include "common.h"
 #include "ir_tile_x3.h"
 #include "launch.h"
 
@@ -114,7 +113,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void i
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = (j < 4 ? lo : up) ? v[j] : 0.f;
     bf16x8 h, m, l;
-    itx_split8(v, h, m, l);
+    x3_split8_pair(v, h, m, l);
     uint8_t* d = Xs + r * XPB + 2 * c0;
     *(bf16x8*)d = h;
     *(bf16x8*)(d + 32) = m;
@@ -153,12 +152,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void i
     {
       const float ev[8] = {wef[0].x, wef[0].y, wef[0].z, wef[0].w, wef[1].x, wef[1].y, wef[1].z, wef[1].w};
       bf16x8 h, m, l;
-      itx_split8(ev, h, m, l);
+      x3_split8_pair(ev, h, m, l);
       a1 = isk_sel(second, m, l);  // [am | al]
       a2 = isk_sel(second, h, m);  // [ah | am]
       a3 = h;                      // [ah | ah]
       const float pv[8] = {wpf[0].x, wpf[0].y, wpf[0].z, wpf[0].w, wpf[1].x, wpf[1].y, wpf[1].z, wpf[1].w};
-      itx_split8(pv, ph, pm, pl);
+      x3_split8_pair(pv, ph, pm, pl);
     }
     const float4 be = bexp;
 
@@ -202,7 +201,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void i
     // ---- project GEMM accumulate (rows = output channels, columns = output pixels), six products over K = 32
     {
       const uint8_t* d = Ds + (mt_p * 16 + col) * ITX_DPB + 16 * kq;
-      acc = itx_mfma(ph, pm, pl, *(const bf16x8*)d, *(const bf16x8*)(d + 64), *(const bf16x8*)(d + 128), acc);
+      acc = x3_mfma(ph, pm, pl, *(const bf16x8*)d, *(const bf16x8*)(d + 64), *(const bf16x8*)(d + 128), acc);
     }
     // no barrier here: the next chunk's expand writes E, which every wave finished reading before the barrier
     // above, and its depthwise writes D only after the next expand barrier, which every wave reaches after

@@ -4,8 +4,8 @@
 //
 // Same tiling and phase structure as ir_f32.hip (one workgroup = a TH x TW output tile of one crop; per chunk
 // of 32 hidden channels: expand GEMM -> fp32 E tile in LDS -> depthwise -> project GEMM accumulate), but the
-// two GEMMs run as six v_mfma_f32_16x16x32_bf16 per operand pair on split planes (v = h + m + l exactly, see
-// conv_x3_lds_kernel) instead of v_mfma_f32_16x16x4_f32: 16 cycles per 16x16x32 step against 8 x 32 for the
+// two GEMMs run as six v_mfma_f32_16x16x32_bf16 per operand pair on split planes (the x3 scheme, x3.h)
+// instead of v_mfma_f32_16x16x4_f32: 16 cycles per 16x16x32 step against 8 x 32 for the
 // exact fp32 instruction, 2.7x less matrix time at fp32-level error (tests/test_fp32_gpu.py, fp64 reference).
 //
 //   X: each wave loads the input pixels of its expand tiles straight from global memory into B-operand
@@ -17,7 +17,7 @@
 // Depthwise phase (two thirds of the kernel's VALU instructions before): at stride 1 every thread computes a
 // vertical strip of four outputs from 18 LDS reads whose six addresses are computed once per kernel (ItxStrip; it
 // was four passes of 9 reads and 9 addresses each, per hidden chunk); at both strides the taps are v_pk_fma_f32 on
-// channel pairs and the D split converts two values at a time (common.h split_bf16x3_pair).  Tap order and
+// channel pairs and the D split converts two values at a time (x3.h split_bf16x3_pair).  Tap order and
 // rounding per output are unchanged, so results are bit-identical to the scalar form.  Measured per batch of 32
 // requests, same box, before -> after (profiles/r7_dw_strips): <1, 8, 16, 2, 1> at 56x56 182.3 -> 149.6 us and at
 // 28x28 71.4 -> 61.0 us, SQ_INSTS_VALU 5.73e7 -> 3.74e7 and SQ_INSTS_LDS 5.81e6 -> 4.37e6 (56x56), bank-conflict
@@ -30,7 +30,6 @@
 #include <stdexcept>
 #include <string>
 
-#include "common.h"
 #include "ir_tile_x3.h"
 #include "launch.h"
 #include "letterbox.h"
@@ -38,8 +37,6 @@
 namespace arena {
 
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // Stride-1 depthwise on the 8 x 16 tile: thread (pixel item pi = tid >> 3, channel group g) owns the vertical
 // strip of four outputs (ox = pi & 15, oy = 4 (pi >> 4) .. + 3).  It reads the strip's 6 rows x 3 columns of the
@@ -158,7 +155,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KS == 1 ? 2
 #pragma unroll
         for (int j = 4; j < 8; ++j) v[j] = 0.f;
       }
-      itx_split8(v, xh[i][ks], xm[i][ks], xl[i][ks]);
+      x3_split8_pair(v, xh[i][ks], xm[i][ks], xl[i][ks]);
     }
   }
 
@@ -213,8 +210,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KS == 1 ? 2
       f32x4 e = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks)
-        e = itx_mfma(__builtin_bit_cast(bf16x8, wexp[ks * 3]), __builtin_bit_cast(bf16x8, wexp[ks * 3 + 1]),
-                     __builtin_bit_cast(bf16x8, wexp[ks * 3 + 2]), xh[i][ks], xm[i][ks], xl[i][ks], e);
+        e = x3_mfma(__builtin_bit_cast(bf16x8, wexp[ks * 3]), __builtin_bit_cast(bf16x8, wexp[ks * 3 + 1]),
+                    __builtin_bit_cast(bf16x8, wexp[ks * 3 + 2]), xh[i][ks], xm[i][ks], xl[i][ks], e);
       const int pix = (tt >> 1) * 16 + col;
       const int hc = nt_e * 16 + 4 * kq;
       // the lane holds hidden channels hc..hc+3 of pixel `pix` (16x16 output layout); its own inside flag
@@ -268,7 +265,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KS == 1 ? 2
         if (pr >= PAIRS) break;
         const int mt = pr / NTO;
         const uint8_t* d = Ds + (mt * 16 + col) * ITX_DPB + 16 * kq;
-        acc[j] = itx_mfma(ah, am, al, *(const bf16x8*)d, *(const bf16x8*)(d + 64), *(const bf16x8*)(d + 128), acc[j]);
+        acc[j] = x3_mfma(ah, am, al, *(const bf16x8*)d, *(const bf16x8*)(d + 64), *(const bf16x8*)(d + 128), acc[j]);
       }
     }
 #pragma unroll
@@ -417,6 +414,7 @@ __global__ __launch_bounds__(256) void ir_stem_x3_kernel(const IrParams p) {
         const int tap = ks * 2 + (kq >> 1);
         const uint8_t* sp = Ss + ((ry + (tap >> 1)) * SW + rx + (tap & 1)) * SPB + (kq & 1) * 16;
         const bf16x8 xk = *(const bf16x8*)sp;
+        // x3_mfma_b1 (x3.h) by hand: through the call the second step's fragment read moves behind the first chain
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ws[ks * 3 + 2]), xk, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ws[ks * 3 + 1]), xk, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ws[ks * 3]), xk, acc, 0, 0, 0);
@@ -458,8 +456,8 @@ __global__ __launch_bounds__(256) void ir_stem_x3_kernel(const IrParams p) {
     const int mt = wave + 4 * j;
     if (mt >= PAIRS) break;
     const uint8_t* d = Ds + (mt * 16 + col) * ITX_DPB + 16 * kq;
-    const f32x4 acc = itx_mfma(pah, pam, pal, *(const bf16x8*)d, *(const bf16x8*)(d + 64), *(const bf16x8*)(d + 128),
-                               f32x4{0.f, 0.f, 0.f, 0.f});
+    const f32x4 acc = x3_mfma(pah, pam, pal, *(const bf16x8*)d, *(const bf16x8*)(d + 64), *(const bf16x8*)(d + 128),
+                              f32x4{0.f, 0.f, 0.f, 0.f});
     const int q = mt * 16 + col;
     const int oy = oy0 + q / TW, ox = ox0 + q % TW;
     const int co = 4 * kq;

@@ -15,7 +15,7 @@
 //      32-deep slab, kx 2 plus zero weights the second); + bias, SiLU, zero outside the 320x320 map (the s2
 //      conv's padding), split into h | m | l planes in LDS;
 //   3. the stride-2 conv on v_mfma_f32_32x32x16_bf16, one 16-deep K step per tap, six partial products per
-//      operand pair (the x3 scheme of halo_x3g.hip); stem columns are stored even-then-odd so that the
+//      operand pair (the x3 scheme, x3.h); stem columns are stored even-then-odd so that the
 //      stride-2 fragment reads of 16 consecutive lanes hit consecutive LDS rows;
 //   4. + bias, SiLU, fp32 NHWC store.
 // Weights are read straight from global memory (L2-resident, 41 KB) into fragment registers at each GEMM's start.
@@ -35,15 +35,13 @@
 #include <stdexcept>
 #include <string>
 
-#include "common.h"
 #include "launch.h"
 #include "letterbox.h"
+#include "x3.h"
 
 namespace arena {
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int SX_TW = 16;                   // output columns per tile
 constexpr int SX_SC = 2 * SX_TW + 1;        // stem columns per tile (33)
@@ -61,11 +59,6 @@ __host__ __device__ constexpr int sx_sr(int TH) { return 2 * TH + 1; }  // stem 
 __host__ __device__ constexpr int sx_in_planes(int SRC) { return SRC == 2 ? 3 : 1; }  // bf16 planes of the input
 __host__ __device__ constexpr int sx_lds_bytes(int TH, int SRC) {
   return (sx_in_planes(SRC) * (sx_sr(TH) + 2) * SX_IC * SX_IP + sx_sr(TH) * SX_SRS) * 2;
-}
-
-__device__ __forceinline__ int sx_xcd_remap(int bx, int nx) {
-  const int q = nx / 8, r = nx % 8, x = bx % 8, y = bx / 8;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + y;
 }
 
 }  // namespace
@@ -86,7 +79,7 @@ __global__ __launch_bounds__(NW * 64) void stem_s2_x3_kernel(const StemFusedPara
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int T2 = p.S / 2, Ho = p.S / 4, Wo = p.S / 4;  // s2d / stem map side, output side
   const int tiles_x = Wo / SX_TW, tiles = (Ho / TH) * tiles_x;
-  const int bx = sx_xcd_remap(blockIdx.x, gridDim.x);
+  const int bx = xcd_remap(blockIdx.x, gridDim.x);
   const int b = bx / tiles;
   const int n_live = p.ctrl != nullptr ? min(p.ctrl->n_images, p.cap) : p.cap;
   if (b >= n_live) return;
@@ -125,7 +118,7 @@ __global__ __launch_bounds__(NW * 64) void stem_s2_x3_kernel(const StemFusedPara
       if (px < NPX) {
         bf16x8 h[2], m[2], l[2];
 #pragma unroll
-        for (int c = 0; c < 16; ++c) {
+        for (int c = 0; c < 16; ++c) {  // x3_split_at (x3.h) by hand: through the call this loop compiles differently
           const float x = c < 12 && ok[j] ? v[j][c] : 0.f;
           const bf16 th = (bf16)x;
           const float rr = x - (float)th;
@@ -248,19 +241,12 @@ __global__ __launch_bounds__(NW * 64) void stem_s2_x3_kernel(const StemFusedPara
           const bf16* xa = sIn + ((sr + ky) * SX_IC + sc + kx) * SX_IP + c0;
           const bf16x8 x = *(const bf16x8*)xa;
           const int s = ky * 2 + sl;
-          if constexpr (SRC == 2) {  // x = the h plane; six partial products, smallest first
+          if constexpr (SRC == 2) {  // x = the h plane
             const bf16x8 xm = *(const bf16x8*)(xa + IN_PL), xl = *(const bf16x8*)(xa + 2 * IN_PL);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[s], xm, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[s], x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[s], xl, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[s], x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[s], xm, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[s], x, acc, 0, 0, 0);
+            acc = x3_mfma(ah[s], am[s], al[s], x, xm, xl, acc);
             continue;
           }
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[s], x, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[s], x, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[s], x, acc, 0, 0, 0);
+          acc = x3_mfma_b1(ah[s], am[s], al[s], x, acc);
         }
       if (!live) continue;
       // lane holds channels 4 kq .. 4 kq + 3 of stem pixel (sr, sc)
@@ -268,15 +254,7 @@ __global__ __launch_bounds__(NW * 64) void stem_s2_x3_kernel(const StemFusedPara
       const bool in = (unsigned)gy < (unsigned)T2 && (unsigned)gx < (unsigned)T2;
       bf16x4 h, m, l;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float v = in ? silu(acc[e] + bb[e]) : 0.f;
-        const bf16 th = (bf16)v;
-        const float rr = v - (float)th;
-        const bf16 tm = (bf16)rr;
-        h[e] = th;
-        m[e] = tm;
-        l[e] = (bf16)(rr - (float)tm);
-      }
+      for (int e = 0; e < 4; ++e) x3_split_at(in ? silu(acc[e] + bb[e]) : 0.f, e, h, m, l);
       bf16* d = sSt + sr * SX_SRS + ((sc & 1) * (SX_SCS / 2) + (sc >> 1)) * SX_SP + 4 * kq;
       *(bf16x4*)d = h;
       *(bf16x4*)(d + 16) = m;
@@ -308,12 +286,7 @@ __global__ __launch_bounds__(NW * 64) void stem_s2_x3_kernel(const StemFusedPara
       const int sr = 2 * r + ky, sc = 2 * c + kx;
       const bf16* xr = sSt + sr * SX_SRS + ((sc & 1) * (SX_SCS / 2) + (sc >> 1)) * SX_SP + 8 * fh;
       const bf16x8 xh = *(const bf16x8*)xr, xm = *(const bf16x8*)(xr + 16), xl = *(const bf16x8*)(xr + 32);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, xm, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, xh, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xl, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, xh, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xm, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xh, acc, 0, 0, 0);
+      acc = x3_mfma(wh, wm, wl, xh, xm, xl, acc);
     }
   };
   // ---- 4. epilogue: lane holds channels 8 g + 4 fh + {0..3} of its pixel

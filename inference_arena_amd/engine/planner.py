@@ -163,7 +163,8 @@ def bf16_bytes(t: torch.Tensor) -> bytes:
 def split_bf16x3(t: torch.Tensor) -> torch.Tensor:
     """fp32 [..., K] -> bf16 [..., 3, K]: planes h = rn(t), m = rn(t - h), l = rn(t - h - m) (round to nearest
     even, as v_cvt_pk_bf16_f32): h + m + l equals t to fp32 rounding.  The operand format of the
-    triple-bf16-split kernels (csrc/kernels/ir_crop_f32.hip)."""
+    triple-bf16-split kernels: the host twin of the split in csrc/kernels/x3.h (tests/test_x3_split.py holds the
+    two to the same bits)."""
     t = t.detach().float()
     h = t.to(torch.bfloat16)
     r = t - h.float()
