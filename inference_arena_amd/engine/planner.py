@@ -90,7 +90,13 @@ class Reserved:
     id: int
 IMAGES, CROPS = 0, 1
 ACT = {None: 0, "none": 0, "silu": 1, "relu6": 2}
+ACT_NAMES = (None, "silu", "relu6")
 ALIGN = 256
+# fields 1.. of an OP_CONV record, in record order (the CONV row of the module docstring; ProgramBuilder.decode_conv)
+CONV_FIELDS = ("x_buf", "x_coff", "x_cs", "H", "W", "Cin", "w_off", "Kpad", "b_off", "y_buf", "y_coff", "y_cs", "Ho", "Wo",
+               "Cout", "Cout_pad", "KH", "KW", "stride", "pad_t", "pad_l", "res_buf", "res_coff", "res_cs", "y2_buf",
+               "y2_coff", "y2_cs", "act", "f32out", "batch_kind", "pw_w_off", "pw_kpad", "pw_b_off", "pw_cout",
+               "pw_cout_pad", "pw_y_buf", "pw_y_coff", "pw_y_cs", "pw_act", "w3_off", "has_w3")
 
 
 def fbits(v: float) -> int:
@@ -448,6 +454,17 @@ class ProgramBuilder:
             # fp32: the weights once more as pre-split bf16 planes for the x3g kernels (fields 40-41)
             rec += [0] * 9 + [self.weights.add(pack_conv_weight_x3(w)), 1]
         self._emit(rec, src, dst, res, dst2, pw_dst)
+
+    @staticmethod
+    def decode_conv(rec) -> dict:
+        """One ``OP_CONV`` record as ``conv`` wrote it -> {field name: int}, the names of ``CONV_FIELDS`` (the CONV
+        row of the module docstring) plus ``f32`` (the record's dtype field).  Buffers are ids (``BUF_NONE``: absent),
+        ``act`` / ``pw_act`` the ``ACT`` numbers (``ACT_NAMES`` names them), ``pw_cout`` 0 without a fused 1x1."""
+        if int(rec[0]) != OP_CONV:
+            raise ValueError(f"decode_conv: op {int(rec[0])} is not OP_CONV")
+        d = {name: int(rec[1 + i]) for i, name in enumerate(CONV_FIELDS)}
+        d["f32"] = int(rec[OP_DTYPE_FIELD])
+        return d
 
     def dwconv(self, src: View, dst: View, w: torch.Tensor, b: torch.Tensor, *, stride: int, act: str = "relu6",
                kind: int = IMAGES) -> None:

@@ -56,8 +56,9 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, stride: in
     consumer tile grown by ``halo`` pixels reads is skipped and keeps its contents (ConvParams.marks).
 
     ``pw=(w2, b2)`` (fp32 3x3 stride-1 only): the Detect-head 1x1 ``w2`` [C2, Cout, 1, 1] is applied to the
-    activated result inside the x3hg epilogue (impl 145 + v) and only its [B, Ho, Wo, C2] output is returned;
-    ``pw_out`` (float32 [B, Ho, Wo, C], optional): write those C2 channels at ``pw_out_coff`` of it instead and
+    activated result inside the x3hg epilogue (impl 145 + v) and only its [B, Ho, Wo, C2] output is returned (a
+    bf16 ``x``: the v3 halo-tile kernel's epilogue, csrc/kernels/conv3x3_v3.hip, bf16 output);
+    ``pw_out`` (float32 / bf16 as the output, [B, Ho, Wo, C], optional): write those C2 channels at ``pw_out_coff`` of it instead and
     return it.  ``gate=(logits, coff, n, gate_min)`` (x3hg fused-1x1 kernels only): float32 ``logits`` with the shape
     of the tensor the 1x1 output is written to; a tile none of whose pixels has ``logits[..., coff:coff + n] >=
     gate_min`` is skipped and keeps its previous contents (ConvParams.gate).
@@ -89,22 +90,26 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, stride: in
     if pw is not None:
         from ..engine.planner import pack_pw_weight_x3
 
-        if not f32:
-            raise ValueError("conv2d_nhwc: the functional fused pointwise path is fp32-only")
         w2, b2 = pw
         co2 = w2.shape[0]
-        k2 = (cout + 31) // 32 * 32
-        w2p = torch.frombuffer(bytearray(pack_pw_weight_x3(w2.detach().cpu().float(), k2)),
-                               dtype=torch.int16).to(x.device)
-        b2p = torch.zeros((co2 + 15) // 16 * 16)
-        b2p[:co2] = b2.detach().float()
-        b2p = b2p.to(x.device)
+        if f32:
+            k2 = (cout + 31) // 32 * 32
+            w2p = torch.frombuffer(bytearray(pack_pw_weight_x3(w2.detach().cpu().float(), k2)),
+                                   dtype=torch.int16).to(x.device)
+            b2p = torch.zeros((co2 + 15) // 16 * 16)
+            b2p[:co2] = b2.detach().float()
+            b2p = b2p.to(x.device)
+        else:  # bf16 (conv3x3_v3.hip): W2 [Cout2_pad][Kpad2] bf16 as the planner packs it, bf16 output
+            if gate is not None:
+                raise ValueError("conv2d_nhwc: the tile gate is an fp32 x3hg option")
+            w2p, b2p, k2, _, _ = pack_weights(w2, b2, x.device, "bf16")
+        pw_dtype = torch.float32 if f32 else torch.bfloat16
         if pw_out is None:
-            out = torch.empty(B, Ho, Wo, co2, dtype=torch.float32, device=x.device)
+            out = torch.empty(B, Ho, Wo, co2, dtype=pw_dtype, device=x.device)
             pw_out_coff = 0
         else:
             out = pw_out
-            if (out.shape[:3] != (B, Ho, Wo) or out.shape[3] < pw_out_coff + co2 or out.dtype != torch.float32
+            if (out.shape[:3] != (B, Ho, Wo) or out.shape[3] < pw_out_coff + co2 or out.dtype != pw_dtype
                     or out.device != x.device or not out.is_contiguous()):
                 raise ValueError(f"conv2d_nhwc: pw_out {tuple(out.shape)} {out.dtype} does not fit the 1x1 output")
         pwd = {"pw_w": _ptr(w2p), "pw_bias": _ptr(b2p), "pw_y": _ptr(out, pw_out_coff), "pw_ys": out.shape[-1],

@@ -1,6 +1,7 @@
 """Statistical error bounds of the fp32 kernels against fp64 references, shared by test_fp32_bounds.py (CPU: proves
 the two tiers reject subtly wrong kernels that the per-element formulas accept) and the fp32 GPU tests
-(test_fp32_gpu.py, test_x3hp_gpu.py, test_ir_s2k16_gpu.py, test_ir_dw_strips_gpu.py, test_native_tensor_gpu.py).
+(test_fp32_gpu.py, test_x3hp_gpu.py, test_ir_s2k16_gpu.py, test_ir_dw_strips_gpu.py, test_native_tensor_gpu.py,
+and test_shipped_convs_gpu.py, whose cases shipped_convs.py generates from the tuning table: ``check(listed=False)``).
 A plain helper module, imported like bf16_bounds.py.
 
 **Why.**  The x3 kernels form a * b from six bf16 products (am bm, al bh, ah bl, am bh, ah bm, ah bh).  Losing one
@@ -253,12 +254,18 @@ def passes(got, case, adds=0) -> bool:
     return mx <= ZMAX[case.family] and rms <= ZRMS[case.family]
 
 
-def check(case: Case, got, what="", adds=0, live=None, rms=True):
+def check(case: Case, got, what="", adds=0, live=None, rms=True, listed=True, hw=None):
     """The two tiers on a kernel's NCHW (pooled: [B, N]) output; ``live``: the leading batch entries to compare.
-    Prints the figures before it asserts."""
-    assert case.key in REFERENCE, f"{case.key}: no REFERENCE row (python tests/fp32_bounds.py prints the table)"
+    Prints the figures before it asserts.  ``listed=False``: a generated case (shipped_convs.py), held to its
+    family's limits without a ``REFERENCE`` row; test_shipped_convs.py asserts on every such case what the rows
+    record for the listed ones.  ``hw=(Ho, Wo)``: the kernel computes only the leading Ho x Wo of the reference map
+    (a conv planned with ``out_hw``)."""
+    assert not listed or case.key in REFERENCE, \
+        f"{case.key}: no REFERENCE row (python tests/fp32_bounds.py prints the table)"
     ref, var, _ = case.refs(adds)
     got = got.detach().double().cpu()
+    if hw is not None:
+        ref, var = ref[..., :hw[0], :hw[1]], var[..., :hw[0], :hw[1]]
     if live is not None:
         got, ref, var = got[:live], ref[:live], var[:live]
     assert got.shape == ref.shape, (got.shape, ref.shape)

@@ -13,6 +13,8 @@ from pathlib import Path
 
 import pytest
 
+from shipped_convs import default_programs as _default_programs  # the 14 default programs, shared
+
 ROOT = Path(__file__).resolve().parents[1]
 
 # ConvParams.impl of an fp32 conv: 119 numbers (the literals of f32_impl_check.cpp)
@@ -36,21 +38,6 @@ def test_f32_impl_check_program():
         assert r.returncode == 0, r.stderr[-4000:]
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and "f32_impl_check: ok" in r.stdout, (r.stdout + r.stderr)[-4000:]
-
-
-def _default_programs():
-    from inference_arena_amd.engine import plans
-    from inference_arena_amd.models.zoo import default_models
-
-    y, m = default_models(0)
-    for dtype in ("fp32", "bf16"):
-        yield "pipeline", dtype, plans.plan_pipeline(y, m, conf_thr=0.5, iou_thr=0.45, dtype=dtype)
-        yield "detector", dtype, plans.plan_detector(y, conf_thr=0.5, iou_thr=0.45, dtype=dtype)
-        yield "classifier", dtype, plans.plan_classifier(m, dtype=dtype)
-        yield "split_detector", dtype, plans.plan_split_detector(y, conf_thr=0.5, iou_thr=0.45, dtype=dtype)
-        yield "split_classifier", dtype, plans.plan_split_classifier(m, dtype=dtype)
-        yield "yolo_raw", dtype, plans.plan_yolo_raw(y, dtype=dtype)
-        yield "mobilenet_raw", dtype, plans.plan_mobilenet_raw(m, dtype=dtype)
 
 
 def test_shipped_entries_of_the_default_programs_hold_valid_impls():
