@@ -41,10 +41,43 @@ ARENA_JHD T descale(T x, int n) {
   return (x + ((T)1 << (n - 1))) >> n;
 }
 
+// The coefficient range of the split decoder.  A block with quantized coefficients c_k and quantizers q_k is
+// reconstructed here only when
+//
+//     S = sum over k of |c_k| * q_k  <=  kCoefRangeLimit;
+//
+// the host half (jpeg_decode_coefs / jpeg_decode_compact) hands every other file to the PIL path.  Within the limit
+// three ways of computing the block agree bit for bit: exact integer arithmetic (idct8<int64_t>), int32 arithmetic
+// (idct8<int32_t>, the GPU's) and libjpeg-turbo's SIMD islow IDCT, which PIL runs and which keeps the dequantized
+// inputs, sums and differences of two of them and the pass-1 results in 16-bit lanes.  The argument, with S_c the
+// share of column c in S (so that the S_c add up to S):
+//
+//   * idct8 before its descale is linear in its inputs.  G = 11363 bounds the weight of any input in any output (the
+//     DC's is 2^13; the largest is in[1]'s in out[0], 12299 - 7373 - 3196 + 9633 = 1.38704 * 2^13), and 25172
+//     (F_3_072711026) the weight of any input in any intermediate value, so every intermediate is at most
+//     25172 * sum |in| in magnitude.
+//   * Pass 1, 16-bit lanes: the products c_k * q_k (pmullw), in0 +- in4, in7 + in3 and in5 + in1 of a column (paddw,
+//     psubw) and, for a block without AC, in0 << 2 (psllw) are at most S, S and 4 S = 23620 < 2^15 in magnitude:
+//     nothing wraps.  The 32-bit lanes, and int32 here, hold at most 25172 * S < 2^28.
+//   * Pass-1 results: |ws[r][c]| <= (G * S_c + 2^10) / 2^11 = 5.54835 * S_c + 1/2, so packing them to int16
+//     (packssdw) does not saturate.
+//   * Pass 2, 16-bit lanes: the sum or difference of two values ws[r][a], ws[r][b] of a row is at most
+//     5.54835 * (S_a + S_b) + 1 <= 5.54835 * 5905 + 1 < 32765 in magnitude: nothing wraps.  The 32-bit lanes hold at
+//     most 25172 * (5.54835 * S + 4) < 2^30.
+//   * So no 16-bit or 32-bit quantity wraps or saturates before the final clamp to 0..255, which all three apply
+//     alike: each computes what exact arithmetic computes.
+//
+// The limit is the largest this argument allows, floor((2^15 - 2) * 2^11 / G), and it is sharp: at S = 5906, with
+// 2953 on each of coefficients (1, 0) and (1, 4), ws[0][0] + ws[0][4] = 32768 wraps in PIL's decode
+// (tests/jpeg_range_cases.py, limit_plus_1).  S grows with the DCT energy of a block, so photographs stay well
+// below the limit, but pixels can pass it: full-swing noise or dither in luma reaches S of about 7000, and such
+// files are handed back.  Of the extreme contents the suite encodes, grey 0 / 255 noise does (beyond()).
+constexpr int32_t kCoefRangeLimit = 5905;
+
 // One 1-D pass of the accurate integer IDCT (jpeg_idct_islow) over in[0..7]; outputs are descaled by `shift`
 // (pass 1: kConstBits - kPass1Bits, pass 2: kConstBits + kPass1Bits + 3).  T is the accumulator type: int64_t
-// reproduces libjpeg's JLONG exactly for any input, int32_t is exact for every coefficient set a real 8-bit
-// image produces (|dequantized coefficient| < 2^15) and is what the GPU uses.
+// reproduces libjpeg's JLONG exactly for any input, int32_t is exact for every block within kCoefRangeLimit (the
+// only ones the decode functions let through) and is what the GPU uses.
 template <typename T>
 ARENA_JHD void idct8(const T in[8], T out[8], int shift) {
   // even part: the rotator is sqrt(2) * c(-6)

@@ -1494,7 +1494,8 @@ void HttpFrontEnd::native_decode(DecodeTask& t) {
     }
     if (coef.capacity() > ((size_t)16 << 20)) std::vector<int16_t>().swap(coef);  // do not pin a huge frame's
   }
-  if (st == JpegStatus::Unsupported) {  // a progressive file only its scans show to be outside the split decoder
+  // a file that only its scans show to be outside the split decoder, or coefficients beyond the exact range
+  if (st == JpegStatus::Unsupported) {
     up.reset();                         // its buffer back to the pool before the PIL decode takes a slot
     return pool_submit(t.conn, t.t0, t.body, t.off, t.len, t.kind);
   }

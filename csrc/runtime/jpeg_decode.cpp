@@ -234,9 +234,51 @@ struct BitReader {
   }
 };
 
-// One 8x8 block: DC difference + AC run/size symbols, coefficients written in natural order.
+// The coefficient range (kernels/jpeg_math.h, kCoefRangeLimit), S = sum |c_k| * q_k <= limit per block.  The block
+// decoders pay one addition per coded coefficient for it: they add up |c_k| over the AC coefficients the stream
+// codes, bound S by |DC| * q_0 + max(q_1..63) * sum |c_k|, and only a block that fails this bound (about one in a
+// hundred of a noisy q90 upload) has its exact sum taken.  That addition is not free: profiles/jpeg_range/README.md
+// has the cost and the cheaper-looking variants that were no cheaper.  The DC enters as the predictor itself, not as
+// the int16 stored: a predictor that has left int16 is far beyond the limit (or meets a zero quantizer, which makes
+// it zero in every arithmetic).
+struct RangeQuant {
+  uint16_t qz[64];  // the component's quantization table in zigzag order
+  uint32_t ac_max;  // its largest AC entry
+};
+inline uint64_t range_term(int v, uint16_t q) { return (uint64_t)(uint32_t)(v < 0 ? -v : v) * q; }
+inline uint64_t range_dc(int pred, uint16_t q) { return (uint64_t)(pred < 0 ? -(int64_t)pred : (int64_t)pred) * q; }
+inline bool range_wide(uint64_t sum) { return sum > (uint64_t)jpegm::kCoefRangeLimit; }
+const char* const kRangeMessage = "coefficients beyond the range in which libjpeg's 16-bit IDCT is exact";
+
+void range_quant(const JpegInfo& info, RangeQuant rq[kJpegMaxComp]) {
+  for (int c = 0; c < info.ncomp; ++c) {
+    rq[c].ac_max = 0;
+    for (int k = 0; k < 64; ++k) {
+      rq[c].qz[k] = info.qt[c][kNatural[k]];
+      if (k) rq[c].ac_max = std::max<uint32_t>(rq[c].ac_max, rq[c].qz[k]);
+    }
+  }
+}
+
+// the exact sum of a dense block (natural order) whose DC predictor is `pred`
+__attribute__((noinline)) bool range_wide_block(const int16_t* blk, int pred, const RangeQuant& rq) {
+  uint64_t sum = range_dc(pred, rq.qz[0]);
+  for (int k = 1; k < 64; ++k) sum += range_term(blk[kNatural[k]], rq.qz[k]);
+  return range_wide(sum);
+}
+
+// the same of a compact block: `vals` are the values of the coefficients `mask` names, in zigzag order, the DC first
+__attribute__((noinline)) bool range_wide_compact(uint64_t mask, const int16_t* vals, int pred, const RangeQuant& rq) {
+  uint64_t sum = range_dc(pred, rq.qz[0]);
+  ++vals;
+  for (uint64_t m = mask & ~1ull; m; m &= m - 1) sum += range_term(*vals++, rq.qz[__builtin_ctzll(m)]);
+  return range_wide(sum);
+}
+
+// One 8x8 block: DC difference + AC run/size symbols, coefficients written in natural order.  `wide` is set (never
+// cleared) when the block is outside the coefficient range.
 __attribute__((always_inline)) inline bool decode_block(BitReader& br, const HuffTable& dc, const HuffTable& ac,
-                                                        int& pred, int16_t* blk) {
+                                                        int& pred, int16_t* blk, const RangeQuant& rq, bool& wide) {
   std::memset(blk, 0, 64 * sizeof(int16_t));
   br.need(32);
   const int s = br.decode(dc);
@@ -245,6 +287,7 @@ __attribute__((always_inline)) inline bool decode_block(BitReader& br, const Huf
     pred += extend(br.get(s), s);
   }
   blk[0] = (int16_t)pred;
+  uint32_t mags = 0;  // sum |c_k| over the coded AC coefficients: at most 63 * 2^15
   for (int k = 1; k < 64;) {
     br.need(32);  // a code (<= 16 bits) and its magnitude (<= 15 bits)
     const int32_t f = ac.ac_fast[br.buf >> (64 - kFastBits)];
@@ -252,7 +295,9 @@ __attribute__((always_inline)) inline bool decode_block(BitReader& br, const Huf
       br.skip(f & 0xFF);
       k += (f >> 8) & 0xFF;
       if (k > 63) break;  // EOB (or a corrupt run past the block)
-      blk[kNatural[k]] = (int16_t)(f >> 16);
+      const int v = f >> 16;
+      blk[kNatural[k]] = (int16_t)v;
+      mags += (uint32_t)(v < 0 ? -v : v);
       ++k;
       continue;
     }
@@ -260,13 +305,17 @@ __attribute__((always_inline)) inline bool decode_block(BitReader& br, const Huf
     const int r = rs >> 4, sz = rs & 15;
     if (sz) {
       k += r;
-      blk[kNatural[k]] = (int16_t)extend(br.get(sz), sz);
+      const int v = extend(br.get(sz), sz);
+      blk[kNatural[k]] = (int16_t)v;
+      mags += (uint32_t)(v < 0 ? -v : v);
       ++k;
     } else {
       if (r != 15) break;  // EOB
       k += 16;
     }
   }
+  if (__builtin_expect(range_wide(range_dc(pred, rq.qz[0]) + (uint64_t)mags * rq.ac_max), 0))
+    wide |= range_wide_block(blk, pred, rq);
   return true;
 }
 
@@ -274,7 +323,8 @@ __attribute__((always_inline)) inline bool decode_block(BitReader& br, const Huf
 // The same block in the compact layout (jpeg_decode.h, jpeg_decode_compact): bit k of *mask set for every coded
 // coefficient at zigzag index k, their values appended to vals in zigzag order (the DC always, even when 0).
 __attribute__((always_inline)) inline bool decode_block_compact(BitReader& br, const HuffTable& dc, const HuffTable& ac,
-                                                                int& pred, uint64_t* mask, int16_t* vals, int64_t& nv) {
+                                                                int& pred, uint64_t* mask, int16_t* vals, int64_t& nv,
+                                                                const RangeQuant& rq, bool& wide) {
   br.need(32);
   const int s = br.decode(dc);
   if (s) {
@@ -284,6 +334,7 @@ __attribute__((always_inline)) inline bool decode_block_compact(BitReader& br, c
   uint64_t m = 1;
   int64_t n = nv;
   vals[n++] = (int16_t)pred;
+  uint32_t mags = 0;  // as in decode_block
   for (int k = 1; k < 64;) {
     br.need(32);
     const int32_t f = ac.ac_fast[br.buf >> (64 - kFastBits)];
@@ -292,7 +343,9 @@ __attribute__((always_inline)) inline bool decode_block_compact(BitReader& br, c
       k += (f >> 8) & 0xFF;
       if (k > 63) break;
       m |= 1ull << k;
-      vals[n++] = (int16_t)(f >> 16);
+      const int v = f >> 16;
+      vals[n++] = (int16_t)v;
+      mags += (uint32_t)(v < 0 ? -v : v);
       ++k;
       continue;
     }
@@ -301,6 +354,7 @@ __attribute__((always_inline)) inline bool decode_block_compact(BitReader& br, c
     if (sz) {
       k += r;
       const int16_t v = (int16_t)extend(br.get(sz), sz);
+      mags += (uint32_t)(v < 0 ? -(int)v : (int)v);
       if (k > 63) {  // a corrupt run past the block: the dense decoder's kNatural pad stores it at 63
         if (m >> 63) vals[n - 1] = v;  // zigzag 63 is the last value appended
         else {
@@ -318,6 +372,8 @@ __attribute__((always_inline)) inline bool decode_block_compact(BitReader& br, c
     }
   }
   *mask = m;
+  if (__builtin_expect(range_wide(range_dc(pred, rq.qz[0]) + (uint64_t)mags * rq.ac_max), 0))
+    wide |= range_wide_compact(m, vals + nv, pred, rq);
   nv = n;
   return true;
 }
@@ -782,6 +838,8 @@ JpegStatus decode_scans(const uint8_t* data, size_t n, const JpegInfo& info, int
   thread_local std::unique_ptr<TableCache> cache;
   if (!cache) cache.reset(new TableCache());
   std::memset(coef, 0, (size_t)info.coef_count * sizeof(int16_t));
+  RangeQuant rq[kJpegMaxComp];
+  range_quant(info, rq);
   JpegHuffSpec dc[4], ac[4];  // DHT between scans redefines them
   for (int i = 0; i < 4; ++i) {
     dc[i] = info.dc[i];
@@ -895,6 +953,7 @@ JpegStatus decode_scans(const uint8_t* data, size_t n, const JpegInfo& info, int
     int pred[kJpegMaxComp] = {0, 0, 0};
     int eobrun = 0;
     int todo = ri;
+    bool wide = false;  // sequential scans: a block outside the coefficient range
     auto block = [&](int i, int16_t* blk) -> bool {
       switch (kind) {
         case 0: return prog_dc_first(br, *tab[i], pred[i], al, blk);
@@ -902,7 +961,7 @@ JpegStatus decode_scans(const uint8_t* data, size_t n, const JpegInfo& info, int
         case 2: return prog_ac_first(br, *tab[i], ss, se, al, eobrun, blk);
         case 3: return prog_ac_refine(br, *tab[i], ss, se, al, eobrun, blk);
         // a whole block as a baseline scan codes it; bits that match no code make libjpeg warn
-        default: return decode_block(br, *tab[i], *actab[i], pred[i], blk) && !br.bad_code;
+        default: return decode_block(br, *tab[i], *actab[i], pred[i], blk, rq[ci[i]], wide) && !br.bad_code;
       }
     };
     int next_rst = 0;
@@ -940,6 +999,7 @@ JpegStatus decode_scans(const uint8_t* data, size_t n, const JpegInfo& info, int
       }
       // a marker cut the segment short and zero bits were read past it: libjpeg warns, and skips what follows
       if (br.starved()) return hand_back(err, "scan data ends early");
+      if (wide) return hand_back(err, kRangeMessage);
     }
     if (br.truncated || br.overran()) {
       err = kTruncated;
@@ -1001,6 +1061,16 @@ JpegStatus decode_scans(const uint8_t* data, size_t n, const JpegInfo& info, int
   for (int c = 0; c < info.ncomp; ++c)
     for (int k = 0; k < 64; ++k)
       if (sent[c][k] != 0) return hand_back(err, "incomplete progression");
+  // the coefficient range, now that every scan has had its say
+  for (int c = 0; c < info.ncomp; ++c) {
+    const JpegCompDesc& d = info.comp[c];
+    const int16_t* blk = coef + d.coef_off;
+    for (int64_t b = 0, nb = (int64_t)d.bw * d.bh; b < nb; ++b, blk += 64) {
+      uint64_t sum = 0;
+      for (int k = 0; k < 64; ++k) sum += range_term(blk[k], info.qt[c][k]);
+      if (range_wide(sum)) return hand_back(err, kRangeMessage);
+    }
+  }
   return JpegStatus::Ok;
 }
 }  // namespace
@@ -1020,6 +1090,9 @@ JpegStatus jpeg_decode_coefs(const uint8_t* data, size_t n, const JpegInfo& info
       return JpegStatus::Corrupt;
     }
   }
+  RangeQuant rq[kJpegMaxComp];
+  range_quant(info, rq);
+  bool wide = false;  // some block is outside the coefficient range: reported once the scan has proved sound
   BitReader br{data + info.scan_begin, data + n};
   int pred[kJpegMaxComp] = {0, 0, 0};
   const bool single = info.ncomp == 1;
@@ -1054,7 +1127,7 @@ JpegStatus jpeg_decode_coefs(const uint8_t* data, size_t n, const JpegInfo& info
       continue;
     }
     if (single) {
-      if (!decode_block(br, *dcp[0], *acp[0], pred[0], coef + m * 64)) {
+      if (!decode_block(br, *dcp[0], *acp[0], pred[0], coef + m * 64, rq[0], wide)) {
         err = "Failed to decode image: bad DC magnitude";
         return JpegStatus::Corrupt;
       }
@@ -1067,7 +1140,7 @@ JpegStatus jpeg_decode_coefs(const uint8_t* data, size_t n, const JpegInfo& info
       for (int v = 0; v < d.v; ++v) {
         int16_t* row = coef + d.coef_off + (((int64_t)my * d.v + v) * d.bw + (int64_t)mx * d.h) * 64;
         for (int h = 0; h < d.h; ++h) {
-          if (!decode_block(br, *dcp[c], *acp[c], pred[c], row + h * 64)) {
+          if (!decode_block(br, *dcp[c], *acp[c], pred[c], row + h * 64, rq[c], wide)) {
             err = "Failed to decode image: bad DC magnitude";
             return JpegStatus::Corrupt;
           }
@@ -1079,6 +1152,10 @@ JpegStatus jpeg_decode_coefs(const uint8_t* data, size_t n, const JpegInfo& info
   if (br.truncated || br.overran()) {
     err = "Failed to decode image: image file is truncated";
     return JpegStatus::Corrupt;
+  }
+  if (wide) {
+    err = kRangeMessage;
+    return JpegStatus::Unsupported;
   }
   return JpegStatus::Ok;
 }
@@ -1168,6 +1245,9 @@ JpegStatus jpeg_decode_compact(const uint8_t* data, size_t n, JpegInfo& info, ui
   const int64_t val_at = (tb * 12 + 15) & ~(int64_t)15;
   int16_t* vals = (int16_t*)(out + val_at);
   int64_t nv = 0;
+  RangeQuant rq[kJpegMaxComp];
+  range_quant(info, rq);
+  bool wide = false;  // as in jpeg_decode_coefs
   BitReader br{data + info.scan_begin, data + n};
   int pred[kJpegMaxComp] = {0, 0, 0};
   const bool single = info.ncomp == 1;
@@ -1181,7 +1261,7 @@ JpegStatus jpeg_decode_compact(const uint8_t* data, size_t n, JpegInfo& info, ui
       masks[gb] = 0;
       return true;
     }
-    return decode_block_compact(br, *dcp[c], *acp[c], pred[c], masks + gb, vals, nv);
+    return decode_block_compact(br, *dcp[c], *acp[c], pred[c], masks + gb, vals, nv, rq[c], wide);
   };
   for (int64_t m = 0; m < n_mcu; ++m) {
     if (ri) {
@@ -1219,6 +1299,10 @@ JpegStatus jpeg_decode_compact(const uint8_t* data, size_t n, JpegInfo& info, ui
   if (br.truncated || br.overran()) {
     err = "Failed to decode image: image file is truncated";
     return JpegStatus::Corrupt;
+  }
+  if (wide) {
+    err = kRangeMessage;
+    return JpegStatus::Unsupported;
   }
   info.compact_bytes = val_at + nv * 2;
   info.cmask_off = 0;

@@ -19,9 +19,14 @@
 // switch off, with an incomplete or inconsistent progression, more than kJpegMaxScans scans or a DQT between scans
 // — is reported as Unsupported and the caller sends the upload to the PIL fallback (server/decode_pool.py).  For a
 // file whose scans are walked (progressive, or sequential in several scans) Unsupported can also come from the
-// decode functions, after jpeg_parse said Ok: callers route it to the same fallback.  The same
-// reconstruction arithmetic is available on the host (jpeg_coefs_to_rgb) as the bit-exact reference of the
-// kernels and as a host-only decode.
+// decode functions, after jpeg_parse said Ok, and for every file when its coefficients are beyond the range in which
+// libjpeg's 16-bit IDCT is exact: some block with sum |c_k| * q_k > kCoefRangeLimit (kernels/jpeg_math.h), where PIL's
+// SIMD decode, exact arithmetic and the kernels' int32 arithmetic are no longer proved to agree.  Photographs stay
+// well within it; blocks of full-swing noise or dither in luma (0 / 255 in all three channels) reach S of about 7000
+// at any quality and are handed back although they come from pixels (and although PIL and the kernels' arithmetic
+// still agree on such dense blocks: the criterion is sufficient, not necessary); a crafted file can carry anything.
+// Callers route either to the same fallback.  The same reconstruction arithmetic is available on the host (jpeg_coefs_to_rgb) as the
+// bit-exact reference of the kernels and as a host-only decode.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -96,7 +101,9 @@ JpegStatus jpeg_parse(const uint8_t* data, size_t n, JpegInfo& info, std::string
 // Entropy-decode the scan: info.coef_count int16 quantized coefficients, natural order, one block after the
 // other (component c's block (by, bx) at comp[c].coef_off + (by * bw + bx) * 64).  A scan cut short by a
 // marker is padded with zero bits (libjpeg's warning, which PIL ignores); a file that simply ends inside the
-// scan is Corrupt ("image file is truncated", as PIL raises), like structurally broken streams.
+// scan is Corrupt ("image file is truncated", as PIL raises), like structurally broken streams.  A sound scan with a
+// block beyond the coefficient range (above) is Unsupported, in every kind of file: single-scan files say so after the
+// scan (a damaged one stays Corrupt), sequential multi-scan files at the block, progressive files after the last scan.
 //
 // A progressive file (info.progressive) is decoded scan by scan into the same dense layout: DC scans interleaved
 // or not, single-component AC scans, first and refinement passes, EOB runs, restart intervals, and tables or a

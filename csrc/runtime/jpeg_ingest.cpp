@@ -146,7 +146,8 @@ void JpegIngest::run(Task& t) {
       }
     }
   }
-  if (st == JpegStatus::Unsupported) {  // a progressive file only its scans show to be outside the split decoder
+  // a file that only its scans show to be outside the split decoder, or coefficients beyond the exact range
+  if (st == JpegStatus::Unsupported) {
     up.reset();                         // its buffer back to the pool
     {
       std::lock_guard<std::mutex> lk(stats_mu_);

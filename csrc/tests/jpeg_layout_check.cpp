@@ -7,13 +7,15 @@
 // coefficient buffer, every chroma read inside its plane and every pixel inside the output, all of which are
 // allocated here at exactly their stated sizes.
 //
-//   jpeg_layout_check <iterations per seed> <seed.jpg>...
+//   jpeg_layout_check <iterations per seed> <seed.jpg>... [--range <seed.jpg>...]
 //
-// Every seed must decode (dense and compact, equal) and reconstruct.  Every mutation is decoded both ways: same
-// status, the payload within jpeg_compact_capacity, and expanded equal to the dense blocks.  Mutations: random byte
-// flips anywhere; byte flips in the frame header's sampling factors and component ids; byte flips inside scan
-// headers; truncation; a scan dropped, duplicated or swapped with its neighbour; a restart interval inserted in
-// front of a scan.
+// Every seed must decode (dense and compact, equal) and reconstruct.  The seeds after --range are files with crafted
+// coefficients on both sides of the decoder's coefficient range (tests/jpeg_range_cases.py), in today's layouts: they
+// must parse, and the dense and the compact decode must agree on "ok" or "unsupported" for them as for their
+// mutations.  Every mutation is decoded both ways: same status, the payload within jpeg_compact_capacity, and
+// expanded equal to the dense blocks.  Mutations: random byte flips anywhere; byte flips in the frame header's
+// sampling factors and component ids; byte flips inside scan headers; truncation; a scan dropped, duplicated or
+// swapped with its neighbour; a restart interval inserted in front of a scan.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -105,16 +107,29 @@ Bytes read_file(const char* path) {
 
 int main(int argc, char** argv) {
   if (argc < 3) {
-    std::fprintf(stderr, "usage: jpeg_layout_check iterations seed.jpg...\n");
+    std::fprintf(stderr, "usage: jpeg_layout_check iterations seed.jpg... [--range seed.jpg...]\n");
     return 2;
   }
   const int iters = std::atoi(argv[1]);
   std::mt19937 rng(9157);
   int counts[3] = {0, 0, 0};
+  int range_seeds[2] = {0, 0};  // ok, unsupported
+  bool range = false;
   for (int a = 2; a < argc; ++a) {
+    if (std::strcmp(argv[a], "--range") == 0) {
+      range = true;
+      continue;
+    }
     const Bytes seed = read_file(argv[a]);
     const int before = new_layouts;
-    if (seed.size() < 4 || run(seed) != JpegStatus::Ok || new_layouts == before) {
+    if (range) {
+      const JpegStatus st = seed.size() < 4 ? JpegStatus::Corrupt : run(seed);
+      if (st == JpegStatus::Corrupt) {
+        std::fprintf(stderr, "seed %s is not a well-formed file\n", argv[a]);
+        return 1;
+      }
+      range_seeds[(int)st]++;
+    } else if (seed.size() < 4 || run(seed) != JpegStatus::Ok || new_layouts == before) {
       std::fprintf(stderr, "seed %s does not decode as one of the layouts under test\n", argv[a]);
       return 1;
     }
@@ -183,7 +198,8 @@ int main(int argc, char** argv) {
     std::printf("jpeg_layout_check: %d decodes are inconsistent (compact vs dense, or the descriptor)\n", mismatches);
     return 1;
   }
-  std::printf("jpeg_layout_check: ok (%d seeds; %d ok, %d unsupported, %d corrupt; compact == dense on all)\n",
-              argc - 2, counts[0], counts[1], counts[2]);
+  std::printf("jpeg_layout_check: ok (%d seeds, %d + %d of them in and beyond the coefficient range; %d ok, "
+              "%d unsupported, %d corrupt; compact == dense on all)\n",
+              argc - 2 - (range ? 1 : 0), range_seeds[0], range_seeds[1], counts[0], counts[1], counts[2]);
   return 0;
 }

@@ -184,31 +184,54 @@ def _blocks(plane, qt):
 def write(planes, sampling=S420, scans=None, restart=0, ids=(1, 2, 3), jfif=True, adobe=None, progressive=False,
           between=None, quality=90) -> bytes:
     """A JPEG whose three components are the channels of `planes` (HxWx3 uint8), component c subsampled by box
-    averaging to its factors sampling[c] = (h, v).  scans: lists of component indices, one SOS each (default: one
-    interleaved scan); a scan of one component is not interleaved.  restart: DRI interval in MCUs (of each scan).
-    ids: component ids.  jfif: write the APP0 segment.  adobe: transform byte of an APP14 Adobe segment, or None.
-    progressive: SOF2 with spectral selection only, every scan of `scans` split into a DC scan and one AC scan per
-    component.  between: {scan index: bytes} inserted in front of that SOS."""
-    app0, qt, dht, codes = _tables(quality)
+    averaging to its factors sampling[c] = (h, v), quantised with the tables PIL uses at `quality`.  The other
+    arguments are write_coefs's."""
+    _, qt, _, _ = _tables(quality)
     H, W = planes.shape[:2]
     hmax, vmax = max(h for h, _ in sampling), max(v for _, v in sampling)
     mcux, mcuy = -(-W // (8 * hmax)), -(-H // (8 * vmax))
     full = np.pad(planes, ((0, mcuy * 8 * vmax - H), (0, mcux * 8 * hmax - W), (0, 0)), mode="edge").astype(np.float64)
-    comps = []
+    blocks = []
     for c, (h, v) in enumerate(sampling):
         assert hmax % h == 0 and vmax % v == 0
         fh, fv = hmax // h, vmax // v
         p = full[:, :, c].reshape(mcuy * 8 * v, fv, mcux * 8 * h, fh).mean(axis=(1, 3))
+        blocks.append(_blocks(np.clip(np.rint(p), 0, 255), qt[0 if c == 0 else 1]))
+    return write_coefs((H, W), blocks, qt, sampling, scans=scans, restart=restart, ids=ids, jfif=jfif, adobe=adobe,
+                       progressive=progressive, between=between)
+
+
+def write_coefs(size, blocks, qt, sampling=S444, pq=(0, 0), scans=None, restart=0, ids=(1, 2, 3), jfif=True,
+                adobe=None, progressive=False, between=None) -> bytes:
+    """A JPEG of size = (H, W) from quantised coefficients: blocks[c] is int[mcuy * v][mcux * h][64] in zigzag order
+    for component c with factors sampling[c] = (h, v); qt = {0: luma table, 1: chroma table}, 64 entries each in
+    zigzag order, written with 16-bit entries (DQT precision Pq = 1) where pq[t] is 1.  The Huffman tables are PIL's
+    (DC differences up to +-2047, AC coefficients up to +-1023): the caller keeps the blocks within them.
+    scans: lists of component indices, one SOS each (default: one interleaved scan); a scan of one component is not
+    interleaved.  restart: DRI interval in MCUs (of each scan).  ids: component ids.  jfif: write the APP0 segment.
+    adobe: transform byte of an APP14 Adobe segment, or None.  progressive: SOF2 with spectral selection only, every
+    scan of `scans` split into a DC scan and one AC scan per component.  between: {scan index: bytes} inserted in
+    front of that SOS."""
+    app0, _, dht, codes = _tables(90)
+    H, W = size
+    hmax, vmax = max(h for h, _ in sampling), max(v for _, v in sampling)
+    mcux, mcuy = -(-W // (8 * hmax)), -(-H // (8 * vmax))
+    comps = []
+    for c, (h, v) in enumerate(sampling):
+        assert hmax % h == 0 and vmax % v == 0
+        b = np.asarray(blocks[c])
+        assert b.shape == (mcuy * v, mcux * h, 64), (c, b.shape)
         cw, ch = -(-W * h // hmax), -(-H * v // vmax)  # the component's size in samples
         comps.append(dict(h=h, v=v, tq=0 if c == 0 else 1, tab=0 if c == 0 else 1, cbw=-(-cw // 8), cbh=-(-ch // 8),
-                          blocks=_blocks(np.clip(np.rint(p), 0, 255), qt[0 if c == 0 else 1])))
+                          blocks=b))
     out = bytearray(b"\xff\xd8")
     if jfif:
         out += app0
     if adobe is not None:
         out += segment(0xEE, b"Adobe" + struct.pack(">HHHB", 100, 0, 0, adobe))
     for t in (0, 1):
-        out += segment(0xDB, bytes([t]) + bytes(int(x) for x in qt[t]))
+        entries = [int(x) for x in qt[t]]
+        out += segment(0xDB, bytes([(pq[t] << 4) | t]) + (struct.pack(">64H", *entries) if pq[t] else bytes(entries)))
     out += segment(0xC2 if progressive else 0xC0, struct.pack(">BHHB", 8, H, W, 3) + b"".join(
         bytes([ids[c], (k["h"] << 4) | k["v"], k["tq"]]) for c, k in enumerate(comps)))
     out += dht

@@ -238,7 +238,8 @@ def test_layout_check_under_address_sanitizer(tmp_path):
     """csrc/tests/jpeg_layout_check.cpp: jpeg_parse, the dense and the compact decode and jpeg_coefs_to_rgb built
     host-only with AddressSanitizer and UndefinedBehaviorSanitizer, run as a program of its own over files of every
     new layout and over seeded mutations of them (frame header, scan headers, scans dropped / repeated / swapped,
-    truncation), every buffer at exactly its stated size."""
+    truncation), every buffer at exactly its stated size.  The files with crafted coefficients of jpeg_range_cases.py
+    are seeds too: the dense and the compact decode agree on which side of the coefficient range a file lies."""
     import os
     import shutil
     import subprocess
@@ -271,9 +272,21 @@ def test_layout_check_under_address_sanitizer(tmp_path):
     p = tmp_path / "prog_410.jpg"
     p.write_bytes(L.write(L.scene(37, 53, 5), L.SAMPLINGS["410"][0], progressive=True))
     seeds.append(str(p))
+    import jpeg_range_cases as R
+
+    crafted = [c for c in R.inside() if c.blocks is not None and not c.name.startswith("random_")]
+    crafted += [c for c in R.inside() if c.name.endswith("_0") and c.name.startswith("random_")]
+    crafted += list(R.outside())
+    seeds.append("--range")
+    for c in crafted:
+        p = tmp_path / f"{c.name}.jpg"
+        p.write_bytes(c.data)
+        seeds.append(str(p))
     r = subprocess.run([str(exe), "240", *seeds], capture_output=True, text=True, timeout=300,
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1",
                                 UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1"))
     report = r.stdout + r.stderr
     assert "Sanitizer" not in report and "runtime error" not in report and r.returncode == 0, report[-6000:]
     assert "jpeg_layout_check: ok" in r.stdout
+    n_out = len(R.outside())
+    assert f"{len(crafted) - n_out} + {n_out} of them in and beyond the coefficient range" in r.stdout, r.stdout
