@@ -756,6 +756,8 @@ PYBIND11_MODULE(_C, m) {
   m.attr("HEAD_SPLIT_MIN_BUCKET") = kHeadSplitMinBucket;
   m.attr("HEAD_SPLIT_BOX_IMPL") = kF32X3HP + kHeadSplitBoxVariant;
   m.attr("HEAD_SPLIT_CLS_IMPL") = kF32X3HP + kHeadSplitClsVariant;
+  m.attr("X3HC_IMPL") = kF32X3HC;  // the X3HC row of kernels/f32_impl.h: first impl, variants
+  m.attr("X3HC_VARIANTS") = kF32X3HCVariants;
   m.attr("MARK_CELL") = kMarkCell;
   m.def("head_mark", &py_head_mark);
   m.def(

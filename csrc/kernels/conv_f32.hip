@@ -1536,6 +1536,7 @@ static bool f32_family_run(F32Family f, const ConvParams& p, hipStream_t s, int 
     case F32Family::X3HRPw: return conv_x3hr_pw(p, s, v);
     case F32Family::X3HP: return conv_x3hp(p, s, v);
     case F32Family::X3GSK: return conv_x3g_sk(p, s, v);
+    case F32Family::X3HC: return conv_x3hc(p, s, v);
     case F32Family::Policy:
     case F32Family::Direct:
     case F32Family::Lds:
@@ -1553,7 +1554,11 @@ void conv2d_f32(const ConvParams& p, hipStream_t s) {
   if ((p.n_lo != 0 || p.n_hi != 0 || p.marks != nullptr) &&
       !(p.pw_w == nullptr && f32_conv_impl_in(p.impl, F32Family::X3HP)))
     throw std::runtime_error("conv2d_f32: an output-channel window or a mark gate needs an x3hp variant");
-  if (p.pw_w != nullptr) {  // fused Detect-head 1x1: only the x3hg epilogue variants implement it
+  if (p.pw_w != nullptr) {  // fused Detect-head 1x1: the x3hg / x3hr epilogue variants and x3hc implement it
+    if (f32_conv_impl_in(p.impl, F32Family::X3HC)) {
+      if (!conv_x3hc(p, s, p.impl - kF32X3HC)) throw std::runtime_error(f32_family(F32Family::X3HC).reject);
+      return;
+    }
     if (f32_conv_impl_in(p.impl, F32Family::X3HRPw)) {
       if (!conv_x3hr_pw(p, s, p.impl - kF32X3HRPw)) throw std::runtime_error(f32_family(F32Family::X3HRPw).reject);
       return;

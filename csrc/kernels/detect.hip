@@ -314,6 +314,7 @@ void prepare_kernels() {
   c3_x3_prepare();
   x3hg_prepare();
   x3hp_prepare();
+  x3hc_prepare();
   stem_s2_f32_prepare();
   ARENA_HIP_CHECK(hipFuncSetAttribute((const void*)sppf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                       160 * 1024));

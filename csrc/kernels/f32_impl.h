@@ -60,7 +60,11 @@ constexpr uint32_t f32_all(int n) { return (1u << n) - 1u; }
      to impl 101 / 102 / 103 / 108 / 109 on every conv they take; variant 9 serves the head split only */             \
   X(X3HP, 191, 10, f32_all(9), "conv2d_f32: not an x3hp-eligible conv (3x3 s1 with pre-split weights)")               \
   /* split-K x3g for small grids (XG_SK_VARIANTS: tile x splits); needs ConvParams.sk_ws */                           \
-  X(X3GSK, 171, 9, f32_all(9), "conv2d_f32: not a split-K x3g-eligible conv (pre-split weights, workspace)")
+  X(X3GSK, 171, 9, f32_all(9), "conv2d_f32: not a split-K x3g-eligible conv (pre-split weights, workspace)")           \
+  /* x3hc: exact 80-channel 16-wide halo tiles for the Detect head's class branch, with or without the fused 1x1    \
+     (halo_x3c.hip HC_VARIANTS) */                                                                                    \
+  X(X3HC, 211, 3, f32_all(3),                                                                                         \
+    "conv2d_f32: not an x3hc-eligible conv (3x3 s1 pad 1, Cin % 16, Cout 80, pre-split weights, fused 1x1 <= 80)")
 
 enum class F32Family {
 #define F32_FAMILY_ID(name, first, count, tuned, reject) name,

@@ -109,6 +109,10 @@ bool conv_x3hg_pw(const ConvParams& p, hipStream_t s, int v);  // v: row of HG_P
 bool x3hp_supported(const ConvParams& p);
 bool conv_x3hp(const ConvParams& p, hipStream_t s, int v);
 void x3hp_prepare();
+// x3hc (halo_x3c.hip): 3x3 s1 pad 1 to exactly 80 channels, with the fused 1x1 when pw_w is set
+bool x3hc_supported(const ConvParams& p);
+bool conv_x3hc(const ConvParams& p, hipStream_t s, int v);
+void x3hc_prepare();
 // fused-1x1 x3hg variant (halo_x3g.hip HG_PW_VARIANTS) that conv2d_f32 runs for ConvParams.impl on a conv with
 // cout_pad padded output channels (kF32X3HGPw + v, kF32X3HGPwSmall + v, 0 = by channel count), -1: none; and its
 // pixel tile

@@ -21,9 +21,9 @@ static int fails = 0;
   } while (0)
 
 int main() {
-  // 1. the valid set: 119 numbers
+  // 1. the valid set: 122 numbers
   static const int kRanges[][2] = {{0, 3},     {10, 26},   {40, 52},   {100, 111}, {111, 131}, {131, 145},
-                                   {145, 151}, {151, 161}, {161, 167}, {171, 180}, {181, 183}, {191, 201}};
+                                   {145, 151}, {151, 161}, {161, 167}, {171, 180}, {181, 183}, {191, 201}, {211, 214}};
   int n_valid = 0;
   for (int v = -1; v < 400; ++v) {
     bool want = false;
@@ -31,11 +31,11 @@ int main() {
     CHECK(f32_conv_impl_valid(v) == want, "impl %d: valid %d, expected %d", v, (int)f32_conv_impl_valid(v), (int)want);
     n_valid += f32_conv_impl_valid(v) ? 1 : 0;
   }
-  CHECK(n_valid == 119, "%d valid impls", n_valid);
-  for (int v : {-1, 3, 9, 26, 39, 52, 99, 167, 168, 169, 170, 180, 183, 190, 201})
+  CHECK(n_valid == 122, "%d valid impls", n_valid);
+  for (int v : {-1, 3, 9, 26, 39, 52, 99, 167, 168, 169, 170, 180, 183, 190, 201, 210, 214})
     CHECK(!f32_conv_impl_valid(v), "impl %d must be invalid", v);
 
-  // 2. the autotune candidates, in order: 87 numbers
+  // 2. the autotune candidates, in order: 90 numbers
   std::vector<int> want = {0,   12,  13,  14,  17,  19,  20,  21,  23,  24,  100, 40,  41,  44,  45,
                            46,  47,  48,  101, 102, 103, 104, 105, 106, 107, 108, 109, 110, 116, 117,
                            118, 120, 126, 127, 128, 130, 131, 132, 133, 135, 137, 138, 139, 140, 141};
@@ -46,7 +46,8 @@ int main() {
   for (int v = 161; v <= 166; ++v) want.push_back(v);
   for (int v = 191; v <= 199; ++v) want.push_back(v);
   for (int v = 171; v <= 179; ++v) want.push_back(v);
-  CHECK(want.size() == 87, "%zu expected candidates", want.size());
+  for (int v = 211; v <= 213; ++v) want.push_back(v);
+  CHECK(want.size() == 90, "%zu expected candidates", want.size());
   CHECK(kF32Candidates.size() == want.size(), "%zu candidates", kF32Candidates.size());
   for (size_t i = 0; i < want.size() && i < kF32Candidates.size(); ++i)
     CHECK(kF32Candidates[i] == want[i], "candidate %zu is %d, expected %d", i, kF32Candidates[i], want[i]);
@@ -67,7 +68,7 @@ int main() {
           "impl %d -> family %s variant %d", v, row.name, fv.v);
     if (v >= 10) CHECK(row.reject[0] != '\0', "family %s has no text", row.name);
   }
-  CHECK(kF32FamilyCount == 24, "%d families", kF32FamilyCount);
+  CHECK(kF32FamilyCount == 25, "%d families", kF32FamilyCount);
   for (const F32FamilyRow& r : kF32Families)
     CHECK(r.count >= 1 && r.count <= 32 && (r.count == 32 || r.tuned >> r.count == 0), "family %s: tuned mask", r.name);
 

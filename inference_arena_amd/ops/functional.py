@@ -68,8 +68,15 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, stride: in
     ``impl`` pins a kernel (0 = the dispatch policy; fp32: 1 direct, 2 LDS, 10 + v LDS tile variant v,
     40 + v triple-bf16-split variant v, 100 halo, 101 split halo, 102 / 103 split halo with 48 / 32-channel
     tiles, 104 / 105 weight-stationary streaming 1x1 (auto / 32-channel tiles), 111 + v the x3g 32x32x16 GEMM
-    over pre-split weights, 191 + v the 16-wide split halo tiles over pre-split weights — the whole table: csrc/kernels/f32_impl.h).
+    over pre-split weights, 191 + v the 16-wide split halo tiles over pre-split weights, 211 + v the exact 80-channel
+    halo tiles of the Detect head's class branch (x3hc, csrc/kernels/halo_x3c.hip: 3x3 stride 1 pad 1, Cin a multiple
+    of 16, Cout 80; with ``pw`` to at most 80 channels the 1x1 is fused; ``window``, ``gate`` and ``marks`` are not
+    x3hc options) — the whole table: csrc/kernels/f32_impl.h).
     """
+    if native().X3HC_IMPL <= int(impl) < native().X3HC_IMPL + native().X3HC_VARIANTS and \
+            not (window is None and gate is None and marks is None):
+        raise ValueError("conv2d_nhwc: window, gate and marks are not x3hc options (the family runs the whole "
+                         "80-channel conv on every tile)")
     f32 = x.dtype == torch.float32
     B, H, W, Cx = x.shape
     cout, cin_w, kh, kw = w.shape
