@@ -185,6 +185,7 @@ void py_ir_block(const py::dict& d) {
   p.x3w = get<int>(d, "x3w", 0);
   p.x_parts = get<int>(d, "x_parts", 0);
   p.y_parts = get<int>(d, "y_parts", 0);
+  p.group = get<int>(d, "group", 0);
   prepare_kernels();
   if (get<int>(d, "f32", 0))
     ir_block_f32(p, stream_of(d));

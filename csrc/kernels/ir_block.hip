@@ -384,6 +384,7 @@ void ir_prepare() {
   ir_wave_prepare();
   ir_crop_prepare();
   ir_crop_f32_prepare();
+  ir_group_x3_prepare();
   ir_f32_prepare();
 #define X(S, TH, TW, MP, E) ir_set_attr<S, TH, TW, MP, E>();
   ARENA_IR_CONFIGS(X)

@@ -432,6 +432,8 @@ void ir_block_f32(const IrParams& p, hipStream_t s) {
     if (!ir_stem_x3(p, s)) ir_stem_f32(p, s);  // x3w: the split-plane kernel (ir_tile_x3.hip)
     return;
   }
+  if (ir_group_x3(p, s)) return;  // stride-1 7x7 blocks planned over groups of crops (ir_group_x3.hip)
+  if (p.group > 1) throw std::runtime_error("ir_block_f32: a crop group on a block the group kernel does not take");
   if (ir_block_crop_f32(p, s)) return;  // 14x14 / 7x7 maps: whole-map x3 kernel (ir_crop_f32.hip)
   if (p.x_parts > 1 || p.y_parts > 1)
     throw std::runtime_error("ir_block_f32: partial-sum tensors belong to the whole-map 14x14 kernel");

@@ -172,12 +172,15 @@ struct IrParams {
   int y_cs, Ho, Wo;
   int B;
   const int* bdev;
-  int x3w;                  // fp32: we / wp pre-split into bf16 [h|m|l] planes for ir_crop_f32.hip
+  int x3w;                  // fp32: we / wp pre-split into bf16 [h|m|l] planes for the x3 kernels (non-zero; the
+                            // executor passes the record's field, which is the group where that is > 1)
   // Hidden-sliced 14x14 blocks (ir_crop_f32.hip only; 0 / 1 = a plain tensor): the input holds x_parts partial
   // sums at channel offsets j * inp (the block input is their sum, j = 0, 1, ... in order), and the block's
   // hidden channels are split over y_parts workgroups per band, each writing its partial output at channel
   // offset j * oup (partial 0 carries the project bias and the residual).
   int x_parts, y_parts;
+  // Stride-1 7x7 blocks (ir_group_x3.hip only; 0 / 1 = off): crops per workgroup of the crop-group kernel.
+  int group;
   // fp32 classifier front end (stem = 1, t = 1 blocks, ir_f32.hip): X is not read from memory but built per
   // tile from the batch's uint8 images: crop gather + ImageNet normalisation (crop_gather_s2d semantics) into a
   // space-to-depth tile in LDS, then the 2x2 stem conv over it (+ bias, ReLU6; zero outside the H x W map).
@@ -204,6 +207,11 @@ bool ir_block_crop_f32_supported(int H, int stride, int inp_pad, int hid_pad, in
 bool ir_tile_x3(const IrParams& p, hipStream_t s);
 bool ir_tile_x3_supported(int stride, int inp_pad, int hid_pad, int oup_pad, int expand);
 void ir_tile_x3_prepare();
+// Crop-group fp32-accurate x3 block for the stride-1 7x7 stage (csrc/kernels/ir_group_x3.hip): behind x3w and
+// IrParams.group > 1; false: not such a block.  A supported shape with a group that is not instantiated throws.
+bool ir_group_x3(const IrParams& p, hipStream_t s);
+bool ir_group_x3_supported(int H, int stride, int inp_pad, int hid_pad, int oup_pad, int expand);
+void ir_group_x3_prepare();
 bool ir_stem_x3(const IrParams& p, hipStream_t s);  // IrParams.stem with x3w: split-plane stem / project weights
 // Stride-2 block with a 16-channel input on K-packed x3 MFMAs over the fp32 weights of ir_block_f32
 // (csrc/kernels/ir_s2k16_x3.hip); false: not that geometry, or switched off
@@ -214,6 +222,7 @@ void set_ir_t14(bool v);  // ARENA_IR_T14=1: stride-1 14x14 blocks use one whole
 void set_ir_crop(bool v);  // ARENA_IR_CROP=0: 7x7-output blocks use the tile kernel (ir_crop.hip)
 void set_ir_crop_split(int v);  // ARENA_IR_CROP_SPLIT: workgroups per crop in ir_crop (1 or 2)
 void set_ir_wave(bool v);  // ARENA_IR_WAVE=0: stride-1 blocks use the block-cooperative kernel
+int irx_effective_parts(int planned, int crops);  // hidden slices a crop capacity uses of the planned ones
 void set_irx_slices_big(int n);  // hidden slices at most for crop capacities > 32 (< 1: ARENA_IRX_SLICES_BIG, default 2)
 void set_irx_parts(int n);  // row bands per crop of the 14x14 whole-map fp32 IR kernel (2, 3, 4; else auto)
 

@@ -781,6 +781,7 @@ void Executor::enqueue_program(const std::vector<OpRecord>& prog, Bucket& bk, Sl
         p.B = batch(r[25]);
         p.bdev = bdev(r[25]);
         p.x3w = (int)r[26];
+        p.group = p.x3w > 1 ? p.x3w : 0;  // field 26 > 1: split-plane weights and that many crops per workgroup
         p.x_parts = (int)r[27];
         p.y_parts = (int)r[28];
         if (!f32 && (p.x_parts > 1 || p.y_parts > 1))

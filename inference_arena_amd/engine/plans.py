@@ -317,6 +317,17 @@ def _sliceable_f32(blk, H: int) -> bool:
     return hid_pad // 32 >= irx_slices() and ir_crop_f32_planned(H, blk.stride, inp_pad, hid_pad, oup_pad, 1)
 
 
+def _group_f32(blk, H: int) -> int:
+    """Crops per workgroup of a block planned on the crop-group kernel (``ARENA_IRX_GROUP``: the stride-1 7x7
+    blocks, csrc/kernels/ir_group_x3.hip), 0: not such a block."""
+    from .planner import ir_group_planned
+
+    if blk.expand is None or blk.inp % 8 or blk.oup % 4:
+        return 0
+    return ir_group_planned(H, blk.stride, (blk.inp + 15) // 16 * 16, (blk.hidden + 31) // 32 * 32,
+                            (blk.oup + 15) // 16 * 16, 1)
+
+
 def fuse_stem_ir_f32_default() -> bool:
     """``ARENA_F32_STEM_IR`` (default 1): fp32 programs run crop gather + stem conv + MobileNetV2 block 1 as one
     kernel (ProgramBuilder.ir_block_stem); the s2d crops and the 112 x 112 x 32 stem map are never stored."""
@@ -400,14 +411,19 @@ def plan_mobilenet(pb: ProgramBuilder, m: MobileNetV2, crops, S: int, mean, std,
         if i == 0 and first_fused:
             continue
         Ho = (H + 2 - 3) // blk.stride + 1
-        if fuse_block(blk, H, fuse_ir):
+        group = _group_f32(blk, H) if pb.f32 and fuse_ir == "f32" else 0
+        if group or fuse_block(blk, H, fuse_ir):
             nxt = m.blocks[i + 1] if i + 1 < len(m.blocks) else None
-            yp = slices if (slices > 1 and _sliceable_f32(blk, H) and nxt is not None
-                            and fuse_block(nxt, Ho, fuse_ir) and _sliceable_f32(nxt, Ho)) else 1
+            if group:  # hidden slices by the same rule: into a next block that is a group block too, never the last
+                yp = slices if (slices > 1 and blk.hidden // 32 >= slices and nxt is not None
+                                and _group_f32(nxt, Ho)) else 1
+            else:
+                yp = slices if (slices > 1 and _sliceable_f32(blk, H) and nxt is not None
+                                and fuse_block(nxt, Ho, fuse_ir) and _sliceable_f32(nxt, Ho)) else 1
             O = pb.tensor(f"m{i}.out", Ho, Ho, blk.oup * yp, kind=CROPS_)
             pb.ir_block(View(cur, 0, blk.inp * parts), View(O, 0, blk.oup * yp),
                         fold(blk.expand) if blk.expand is not None else None, fold(blk.dw), fold(blk.project),
-                        stride=blk.stride, res=blk.use_res, kind=CROPS_, x_parts=parts, y_parts=yp)
+                        stride=blk.stride, res=blk.use_res, kind=CROPS_, x_parts=parts, y_parts=yp, group=group)
             cur, H, parts = O, Ho, yp
             continue
         if parts != 1:

@@ -86,6 +86,16 @@ def ir_crop_f32_supported(H: int, stride: int, inp_pad: int, hid_pad: int, oup_p
             and (Ho, stride, inp_pad, oup_pad) in IR_CROP_F32_CONFIGS)
 
 
+# oup_pad -> crops per workgroup instantiated in csrc/kernels/ir_group_x3.hip ARENA_IRG_CONFIGS
+IR_GROUP_X3_GROUPS = {160: (2, 4), 320: (2,)}
+
+
+def ir_group_x3_supported(H: int, stride: int, inp_pad: int, hid_pad: int, oup_pad: int, expand: int) -> bool:
+    """Mirror of arena::ir_group_x3_supported (crop-group x3 kernel for the stride-1 7x7 blocks)."""
+    return (bool(expand) and H == 7 and stride == 1 and inp_pad == 160 and oup_pad in IR_GROUP_X3_GROUPS
+            and hid_pad % 32 == 0)
+
+
 def validate_program(prog: Program, B: int, crop_cap: int, *, max_det: int, cand_cap: int,
                      raw_out_bytes: int | None = None, pool_bytes_per_image: int | None = None) -> None:
     """Static bounds / geometry check of every op.  ``pool_bytes_per_image``: the executor's image pool per batch
@@ -183,14 +193,21 @@ def validate_program(prog: Program, B: int, crop_cap: int, *, max_det: int, cand
             if inp_pad % (16 if f32 else 32) or hid_pad % 32 or oup_pad % 16 or inp > inp_pad or oup > oup_pad \
                     or inp % (4 if f32 else 8):
                 raise ProgramError(f"op {i}: bad ir_block channel geometry")
-            x3w = int(r[26])
+            x3w = int(r[26])  # > 1: split-plane weights and that many crops per workgroup (ir_group_x3.hip)
+            group = x3w if x3w > 1 else 0
             if any(int(v) for v in r[29:31]):
                 raise ProgramError(f"op {i}: ir_block fields 29-30 are reserved (0)")
             xp, yp = max(1, int(r[27])), max(1, int(r[28]))
             if (xp > 1 or yp > 1) and not (f32 and x3w and H == W and H in (14, 7) and max(xp, yp) <= 8
                                            and yp <= hid_pad // 32 and inp % 4 == 0 and oup % 4 == 0):
                 raise ProgramError(f"op {i}: partial-sum ir_block tensors need the fp32 14x14 whole-map kernel")
-            if x3w and not (f32 and (int(r[31]) or (H == W and ir_crop_f32_supported(H, S, inp_pad, hid_pad, oup_pad,
+            # a group op indexes crops [0, n) only: a workgroup's crops at or past the live count (<= n), the last
+            # group's padding included, are neither read nor written, so the views below bound it as they stand
+            if group and not (f32 and H == W and not int(r[31])
+                              and ir_group_x3_supported(H, S, inp_pad, hid_pad, oup_pad, int(r[12]))
+                              and group in IR_GROUP_X3_GROUPS[oup_pad]):
+                raise ProgramError(f"op {i}: no crop-group kernel for groups of {group} on this block")
+            if x3w and not group and not (f32 and (int(r[31]) or (H == W and ir_crop_f32_supported(H, S, inp_pad, hid_pad, oup_pad,
                                                                                       int(r[12])))
                                      or ir_tile_x3_supported(S, inp_pad, hid_pad, oup_pad, int(r[12])))):
                 raise ProgramError(f"op {i}: split-plane weights for a block no x3 kernel takes")

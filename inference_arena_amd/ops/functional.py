@@ -197,14 +197,17 @@ def dwconv3x3_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, stride:
 
 def ir_block_nhwc(x: torch.Tensor, expand, dw, project, *, stride: int, res: bool = False,
                   bdev: torch.Tensor | None = None, x_parts: int = 1, y_parts: int = 1,
-                  out: torch.Tensor | None = None) -> torch.Tensor:
+                  out: torch.Tensor | None = None, group: int = 0) -> torch.Tensor:
     """Fused MobileNetV2 inverted residual (expand 1x1+ReLU6 -> dw3x3+ReLU6 -> project 1x1 [+x]).
     ``expand``/``dw``/``project`` are (weight, bias) pairs with BN folded; ``expand`` None for t=1.
     ``x_parts`` / ``y_parts`` (fp32 14x14 whole-map kernel): ``x`` holds x_parts partial sums of the input side by
     side on the channel axis; the result holds y_parts partial sums (hidden channels split over workgroups).
     ``out``: a contiguous [B, Ho, Wo, >= oup * y_parts] tensor to write into (its last extent is the output's
-    channel stride; channels past the block's are left as they are) instead of a fresh one."""
+    channel stride; channels past the block's are left as they are) instead of a fresh one.
+    ``group`` > 1 (fp32 stride-1 7x7 blocks): the crop-group kernel (csrc/kernels/ir_group_x3.hip) with that many
+    crops per workgroup; ValueError for a block it does not take."""
     from ..engine.planner import ir_x3_plan, pack_ir_weights, split_bf16x3
+    from ..engine.validate import IR_GROUP_X3_GROUPS, ir_group_x3_supported
 
     B, H, W, Ct = x.shape
     C = Ct // x_parts
@@ -215,6 +218,12 @@ def ir_block_nhwc(x: torch.Tensor, expand, dw, project, *, stride: int, res: boo
         x3w, inp_x3 = ir_x3_plan(H, W, stride, C, pk["hid_pad"], pk["oup_pad"], int(expand is not None))
         if x3w and inp_x3 != pk["inp_pad"]:
             pk = pack_ir_weights(expand, dw, project, C, k_align=32)
+    if group > 1:
+        if not (f32 and H == W and ir_group_x3_supported(H, stride, pk["inp_pad"], pk["hid_pad"], pk["oup_pad"],
+                                                         int(expand is not None))
+                and group in IR_GROUP_X3_GROUPS[pk["oup_pad"]]):
+            raise ValueError(f"ir_block_nhwc: no crop-group kernel for groups of {group} on this block")
+        x3w = 1
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     y = out if out is not None else torch.empty(B, Ho, Wo, pk["oup"] * y_parts, dtype=x.dtype, device=x.device)
     if (y.shape[:3] != (B, Ho, Wo) or y.shape[3] < pk["oup"] * y_parts or y.dtype != x.dtype or y.device != x.device
@@ -231,7 +240,7 @@ def ir_block_nhwc(x: torch.Tensor, expand, dw, project, *, stride: int, res: boo
                        "expand": int(expand is not None), "res": int(res),
                        **{k: _ptr(v) for k, v in dev.items()}, "y": _ptr(y), "y_cs": y.shape[3], "Ho": Ho,
                        "Wo": Wo, "B": B, "bdev": _ptr(bdev), "stream": _stream(), "f32": int(f32), "x3w": x3w,
-                       "x_parts": x_parts, "y_parts": y_parts})
+                       "x_parts": x_parts, "y_parts": y_parts, "group": int(group) if group > 1 else 0})
     torch.cuda.synchronize(x.device)  # keep the packed weights alive until the kernel ran
     return y
 

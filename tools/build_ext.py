@@ -39,6 +39,7 @@ SOURCES = [
     "kernels/stem_x3.hip",
     "kernels/ir_f32.hip",
     "kernels/ir_crop_f32.hip",
+    "kernels/ir_group_x3.hip",
     "kernels/ir_tile_x3.hip",
     "kernels/ir_s2k16_x3.hip",
     "kernels/dwconv.hip",
@@ -82,8 +83,11 @@ SOURCES = [
 # (tests/test_x3_split.py holds both split forms to the planner's), scratch 0 either way, 155 / 156 VGPRs instead of
 # 151 / 152 in the 8 x 16 tile and no difference in the other two.  The kernels measured before keep their form (x3.h:
 # a kernel's split form changes only with a measurement).  The host pass takes the feature switch without effect.
+# ir_group_x3.hip, new as well, is built the same way for the same reason: 228 / 253 / 252 VGPRs and no scratch in its
+# three instantiations; with packed ops 228 / 256 / 252 and 16 bytes of scratch a lane in <4, 10>.
 PER_FILE_FLAGS: dict[str, list[str]] = {
     "halo_x3c.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "ir_group_x3.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 
