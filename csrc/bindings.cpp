@@ -102,6 +102,8 @@ void py_conv2d(const py::dict& d) {
   p.w3 = ptr<const void*>(d, "w3");
   p.sk_ws = ptr<float*>(d, "sk_ws");
   p.sk_ws_bytes = get<int64_t>(d, "sk_ws_bytes", 0);
+  p.x_planes = get<int>(d, "x_planes", 0);
+  p.y3 = ptr<void*>(d, "y3");
   prepare_kernels();  // dynamic-LDS limits of the x3 halo / fused kernels (before any launch)
   if (get<int>(d, "f32", 0))
     conv2d_f32(p, stream_of(d));
@@ -976,6 +978,7 @@ PYBIND11_MODULE(_C, m) {
              return e.submit_device(imgs, dets);
            })
       .def("conv_choices", &Executor::conv_choices)
+      .def("planes_ops", &Executor::planes_ops)
       .def("exec_order", &Executor::exec_order, py::arg("B"),
            "program op indices in the order bucket B's graphs launch them")
       .def("gated_ops", &Executor::gated_ops, py::arg("B"), "ops of bucket B that run with a tile gate")

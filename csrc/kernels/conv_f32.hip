@@ -1554,6 +1554,13 @@ void conv2d_f32(const ConvParams& p, hipStream_t s) {
   if ((p.n_lo != 0 || p.n_hi != 0 || p.marks != nullptr) &&
       !(p.pw_w == nullptr && f32_conv_impl_in(p.impl, F32Family::X3HP)))
     throw std::runtime_error("conv2d_f32: an output-channel window or a mark gate needs an x3hp variant");
+  if (p.x_planes != 0 || p.y3 != nullptr) {  // x3 planes in and / or out: x3gp on the tile the X3G impl names
+    if (!f32_conv_impl_in(p.impl, F32Family::X3G))
+      throw std::runtime_error("conv2d_f32: x3 planes (x_planes / y3) need an impl of the x3g family, not impl " +
+                               std::to_string(p.impl));
+    conv_x3gp(p, s, p.impl - kF32X3G);
+    return;
+  }
   if (p.pw_w != nullptr) {  // fused Detect-head 1x1: the x3hg / x3hr epilogue variants and x3hc implement it
     if (f32_conv_impl_in(p.impl, F32Family::X3HC)) {
       if (!conv_x3hc(p, s, p.impl - kF32X3HC)) throw std::runtime_error(f32_family(F32Family::X3HC).reject);

@@ -79,6 +79,12 @@ struct ConvParams {
   float* sk_ws;
   int64_t sk_ws_bytes;
   int sk_splits;
+  // x3 planes (gemm_x3p.hip, fp32 programs): an fp32-accurate activation stored as [pixel][C / 32] chunks of
+  // [h 32 | m 32 | l 32] bf16, the row format of w3.  x_planes: x is such a tensor over exactly Cin channels (pixel
+  // stride Cin / 32 chunks; xs is not read).  y3: the output's planes over exactly Cout channels (Cout % 32 == 0),
+  // written next to y, or alone when y is nullptr.  Either one needs an impl of the X3G family.
+  int x_planes;
+  void* y3;
 };
 void conv2d(const ConvParams& p, hipStream_t s);
 void conv_igemm(const ConvParams& p, hipStream_t s);  // LDS-pipelined implicit GEMM (impl 3)
@@ -102,6 +108,10 @@ bool x3g_supported(const ConvParams& p);
 bool conv_x3g(const ConvParams& p, hipStream_t s, int v);
 bool conv_x3g_sk(const ConvParams& p, hipStream_t s, int v);  // runs the tile unsplit where sk_ws cannot hold the conv
 void x3g_prepare();
+// x3gp (gemm_x3p.hip): tile v (XG_VARIANTS 0..9; v + 10 is the same tile) of the x3g GEMM reading and / or writing
+// x3 planes (ConvParams.x_planes, y3); throws std::runtime_error naming what it does not take
+void conv_x3gp(const ConvParams& p, hipStream_t s, int v);
+void x3gp_prepare();
 bool x3hg_supported(const ConvParams& p);
 bool conv_x3hg(const ConvParams& p, hipStream_t s, int v);
 void x3hg_prepare();

@@ -534,6 +534,18 @@ void Executor::launch_graph(Bucket& bk, int s, hipStream_t st, int n_live) {
   if (staggered) last_launched_ = s;
 }
 
+bool Executor::planes_write(const Bucket& bk, size_t i) const {
+  return i < prog_.size() && i < bk.impl.size() && prog_[i][0] == OP_CONV && prog_[i][kDtypeField] == 1 &&
+         prog_[i][42] > 0 && f32_conv_impl_in(bk.impl[i], F32Family::X3G);
+}
+
+bool Executor::planes_read(const Bucket& bk, size_t i) const {
+  if (i >= prog_.size() || i >= bk.impl.size() || prog_[i][0] != OP_CONV || prog_[i][43] <= 0) return false;
+  const int64_t src = prog_[i][44] - 1;
+  return src >= 0 && (size_t)src < i && prog_[(size_t)src][42] == prog_[i][43] && planes_write(bk, (size_t)src) &&
+         f32_conv_impl_in(bk.impl[i], F32Family::X3G);
+}
+
 uint8_t* Executor::resolve(Bucket& bk, Slot& sl, int64_t buf, int64_t coff, int eb) {
   uint8_t* base = nullptr;
   switch (buf) {
@@ -724,6 +736,15 @@ void Executor::enqueue_program(const std::vector<OpRecord>& prog, Bucket& bk, Sl
           if (!conv_x3hp(p, s, box ? kHeadSplitBoxVariant : kHeadSplitClsVariant))
             throw std::runtime_error("executor: the split first head conv does not fit its x3hp window kernel");
           break;
+        }
+        // x3 planes (fields 42-44): resolved per bucket from the chosen kernels (planes_write / planes_read); not in
+        // autotune's single-op runs (force_impl), whose producer has not run
+        if (f32 && !force_impl) {
+          if (planes_write(bk, gi)) p.y3 = resolve(bk, sl, r[42], 0, 2);
+          if (planes_read(bk, gi)) {
+            p.x = resolve(bk, sl, r[43], 0, 2);
+            p.x_planes = 1;
+          }
         }
         if (f32)
           conv2d_f32(p, s);

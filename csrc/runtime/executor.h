@@ -312,6 +312,25 @@ class Executor : public BatchInstance {
     if (it == buckets_.end()) return {};
     return std::vector<int>(it->second.impl.begin(), it->second.impl.end());
   }
+  // x3 planes (OP_CONV fields 42-44, ARENA_X3_PLANES programs): {ops that read, ops that write} an activation as
+  // planes in bucket B's graphs.  A conv writes planes iff its record has a planes buffer and its chosen impl is in
+  // the x3g family; it reads them iff its producer writes them and its own impl is in that family.
+  std::pair<int, int> planes_ops(int B) const {
+    auto it = buckets_.find(B);
+    std::pair<int, int> n{0, 0};
+    if (it == buckets_.end()) return n;
+    for (size_t i = 0; i < prog_.size(); ++i) {
+      n.first += (int)planes_read(it->second, i);
+      n.second += (int)planes_write(it->second, i);
+    }
+    return n;
+  }
+
+ private:
+  bool planes_write(const Bucket& bk, size_t i) const;
+  bool planes_read(const Bucket& bk, size_t i) const;
+
+ public:
 
  private:
   void enqueue_results_d2h(Bucket& bk, Slot& sl, int n);

@@ -22,6 +22,9 @@ Op record layouts (index: field) — keep in sync with executor.cpp:
          31 pw_w_off 32 pw_kpad 33 pw_b_off 34 pw_cout (0 = none) 35 pw_cout_pad 36 pw_y_buf 37 pw_y_coff
          38 pw_y_cs 39 pw_act   (pointwise conv fused into the 3x3 epilogue; y_buf may then be BUF_NONE)
          40 w3_off 41 has_w3 (fp32: weights pre-split into bf16 planes, pack_conv_weight_x3)
+         42 y3_buf 43 x3_buf 44 x3_src_op 45 reserved (0)   (ARENA_X3_PLANES, fp32: the output / the input also
+         exists as x3 planes, csrc/kernels/gemm_x3p.hip; a planes buffer is never buffer 0, so 0 = none;
+         x3_src_op = index in the whole program of the conv that writes x3_buf, + 1)
   DWCONV 1 x_buf 2 x_coff 3 x_cs 4 H 5 W 6 C 7 w_off 8 b_off 9 y_buf 10 y_coff
          11 y_cs 12 Ho 13 Wo 14 stride 15 act 16 batch_kind
   SPPF   1 buf 2 coff 3 cs 4 H 5 W 6 C 7 batch_kind
@@ -98,6 +101,8 @@ CONV_FIELDS = ("x_buf", "x_coff", "x_cs", "H", "W", "Cin", "w_off", "Kpad", "b_o
                "Cout", "Cout_pad", "KH", "KW", "stride", "pad_t", "pad_l", "res_buf", "res_coff", "res_cs", "y2_buf",
                "y2_coff", "y2_cs", "act", "f32out", "batch_kind", "pw_w_off", "pw_kpad", "pw_b_off", "pw_cout",
                "pw_cout_pad", "pw_y_buf", "pw_y_coff", "pw_y_cs", "pw_act", "w3_off", "has_w3")
+# fields 42.. of an OP_CONV record: the x3 planes of ARENA_X3_PLANES programs (all 0 in every other record)
+CONV_X3_FIELDS = ("y3_buf", "x3_buf", "x3_src_op")
 
 
 def fbits(v: float) -> int:
@@ -280,6 +285,13 @@ def pack_ir_weights(expand, dw, project, inp: int, k_align: int = 32) -> dict:
             "hid_pad": hid_pad, "oup": oup, "oup_pad": oup_pad}
 
 
+def x3_planes_enabled() -> bool:
+    """``ARENA_X3_PLANES`` (default 0): fp32 programs give every qualifying conv -> conv edge a second copy of the
+    activation as x3 planes (OP_CONV fields 42-44); the executor then runs producer and consumer on the x3gp kernels
+    (csrc/kernels/gemm_x3p.hip) where both are tuned to the x3g family.  Off: programs are unchanged."""
+    return os.environ.get("ARENA_X3_PLANES", "0").lower() not in ("0", "false", "no", "off", "")
+
+
 def ir_crop_f32_policy() -> str:
     """``ARENA_IRC_F32``: ``auto`` (default), ``all``/``1`` or ``none``/``0`` — which fp32 MobileNetV2 14x14 / 7x7
     blocks run as the fused x3 kernel (csrc/kernels/ir_crop_f32.hip).  ``auto`` takes the stride-1 14x14 blocks,
@@ -379,6 +391,11 @@ class ProgramBuilder:
         self.cls_start: int | None = None
         self.weights = WeightPacker()
         self.meta: dict = {"dtype": dtype}
+        # x3 planes (ARENA_X3_PLANES): buffer id -> (op, coff, C, H, W, batch kind) of the qualifying conv that last
+        # wrote a view of it, and the (producer op, consumer op) edges found; build() turns the edges into buffers
+        self.x3_planes = self.f32 and x3_planes_enabled()
+        self._x3_out: dict[int, tuple[int, ...]] = {}
+        self._x3_edges: list[tuple[int, int]] = []
 
     def _bf16_only(self, what: str) -> None:
         if self.f32:
@@ -410,6 +427,11 @@ class ProgramBuilder:
 
     def _emit(self, rec: list[int], *touch) -> None:
         self._touch(*touch)
+        if rec[0] != OP_CONV:  # an op that is not a conv and touches a buffer ends the tracking of its conv output
+            for v in touch:
+                b = v.buf if isinstance(v, View) else v
+                if isinstance(b, Buffer):
+                    self._x3_out.pop(b.id, None)
         if len(rec) > OP_DTYPE_FIELD - 1:  # field 46 is reserved (0)
             raise ValueError("op record overlaps the reserved / dtype fields")
         r = list(rec) + [0] * (OP_FIELDS - len(rec))
@@ -475,16 +497,35 @@ class ProgramBuilder:
         elif self.f32 and src.bid != BUF_POOL:
             # fp32: the weights once more as pre-split bf16 planes for the x3g kernels (fields 40-41)
             rec += [0] * 9 + [self.weights.add(pack_conv_weight_x3(w)), 1]
+        if self.x3_planes:
+            self._x3_track(rec, src, dst, dst2, pw_dst, (H, W), (Ho, Wo), kind)
         self._emit(rec, src, dst, res, dst2, pw_dst)
+
+    def _x3_track(self, rec, src, dst, dst2, pw_dst, in_hw, out_hw, kind) -> None:
+        """x3 planes edges: this conv reads planes when its source view is exactly what a qualifying conv wrote
+        (same buffer, channel slice and map), and qualifies as a producer itself when it has pre-split weights, no
+        fused 1x1, no second output and whole 32-channel chunks."""
+        i = len(self.ops)
+        # what conv_x3gp takes: pre-split weights, no fused 1x1, no upsampled copy, 1x1 / 3x3, stride 1 / 2
+        has_w3 = (len(rec) > 41 and rec[41] == 1 and rec[34] == 0 and dst2 is None
+                  and (rec[17], rec[18]) in ((1, 1), (3, 3)) and rec[19] in (1, 2))
+        ent = self._x3_out.get(src.bid)
+        if has_w3 and ent is not None and ent[1:] == (src.coff, src.C, *in_hw, kind):
+            self._x3_edges.append((ent[0], i))
+        for v in (dst, dst2, pw_dst):  # whatever this conv writes replaces what was tracked for that buffer
+            if v is not None:
+                self._x3_out.pop(v.bid, None)
+        if has_w3 and dst.C % 32 == 0 and isinstance(dst.buf, Buffer):
+            self._x3_out[dst.bid] = (i, dst.coff, dst.C, *out_hw, kind)
 
     @staticmethod
     def decode_conv(rec) -> dict:
         """One ``OP_CONV`` record as ``conv`` wrote it -> {field name: int}, the names of ``CONV_FIELDS`` (the CONV
-        row of the module docstring) plus ``f32`` (the record's dtype field).  Buffers are ids (``BUF_NONE``: absent),
+        row of the module docstring) and ``CONV_X3_FIELDS`` (0: no planes) plus ``f32`` (the record's dtype field).  Buffers are ids (``BUF_NONE``: absent),
         ``act`` / ``pw_act`` the ``ACT`` numbers (``ACT_NAMES`` names them), ``pw_cout`` 0 without a fused 1x1."""
         if int(rec[0]) != OP_CONV:
             raise ValueError(f"decode_conv: op {int(rec[0])} is not OP_CONV")
-        d = {name: int(rec[1 + i]) for i, name in enumerate(CONV_FIELDS)}
+        d = {name: int(rec[1 + i]) for i, name in enumerate(CONV_FIELDS + CONV_X3_FIELDS)}
         d["f32"] = int(rec[OP_DTYPE_FIELD])
         return d
 
@@ -772,6 +813,19 @@ class ProgramBuilder:
         for b in self.buffers:
             if b.pinned and b.last >= 0:
                 b.last = n
+        # x3 planes: one buffer of 6 bytes per element per producer, appended after every other buffer so that the
+        # ids, and with them the tuning fingerprint (engine/tuning.py), are those of the plain program
+        planes: dict[int, Buffer] = {}
+        for prod, cons in self._x3_edges:
+            pr = self.ops[prod]
+            if prod not in planes:
+                planes[prod] = self.raw(f"x3planes.op{prod}", pr[13] * pr[14] * pr[15] * 6, pr[30])
+                planes[prod].first = prod
+                pr[42] = planes[prod].id
+            planes[prod].last = max(planes[prod].last, cons)
+            self.ops[cons][43] = planes[prod].id
+            self.ops[cons][44] = prod + 1
+        self._x3_edges = []
         ops = np.asarray(self.ops, dtype=np.int64).reshape(n, OP_FIELDS)
         cs = self.cls_start if self.cls_start is not None else n
         cls_ops = ops[cs:].copy()

@@ -40,8 +40,13 @@ def table_path() -> Path:
 
 
 def fingerprint(ops: np.ndarray) -> str:
-    """Program identity: the op records (kinds, shapes, buffer ids, weight offsets), not the weight values."""
+    """Program identity: the op records (kinds, shapes, buffer ids, weight offsets), not the weight values.
+
+    OP_CONV fields 42-45 (x3 planes, ``ARENA_X3_PLANES``) are left out: a planes program runs the kernel choices
+    of its plain twin, whose records are otherwise the same, and so finds that twin's entries."""
     a = np.array(ops, dtype=np.int64)
+    if a.ndim == 2 and a.shape[1] > 45:
+        a[a[:, 0] == 1, 42:46] = 0  # planner.OP_CONV
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()[:24]
 
 

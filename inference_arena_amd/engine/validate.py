@@ -179,6 +179,26 @@ def validate_program(prog: Program, B: int, crop_cap: int, *, max_det: int, cand
                 if not f32 or int(r[41]) != 1:
                     raise ProgramError(f"op {i}: pre-split weights belong to fp32 convs")
                 weights(i, int(r[40]), KH * KW * ((Cin + 31) // 32) * Cpad * 192, "conv x3 weight")
+            # x3 planes (fields 42-44; 0 = none): 6 bytes per element, whole 32-channel chunks, owned by one conv
+            y3, x3, src_op = int(r[42]), int(r[43]), int(r[44])
+            if int(r[45]) or (x3 != 0) != (src_op != 0):
+                raise ProgramError(f"op {i}: bad x3 planes fields")
+            if (y3 or x3) and not (f32 and int(r[41]) == 1 and int(r[34]) == 0):
+                raise ProgramError(f"op {i}: x3 planes belong to fp32 convs with pre-split weights and no fused 1x1")
+            if y3:
+                if y3 < 0 or Cout % 32 or int(r[25]) != BUF_NONE:
+                    raise ProgramError(f"op {i}: an x3 planes output needs Cout % 32 == 0 and no upsampled output")
+                need(i, y3, 0, n * Ho * Wo * Cout * 6, "conv x3 planes output")
+            if x3:
+                if x3 < 0 or Cin % 32:
+                    raise ProgramError(f"op {i}: an x3 planes input needs Cin % 32 == 0")
+                need(i, x3, 0, n * H * W * Cin * 6, "conv x3 planes input")
+                pr = prog.ops[src_op - 1] if 0 < src_op <= i else None
+                if pr is None or int(pr[0]) != OP_CONV or int(pr[42]) != x3 or \
+                        (int(pr[10]), int(pr[11]), int(pr[13]), int(pr[14]), int(pr[15]), int(pr[30])) != \
+                        (int(r[1]), int(r[2]), H, W, Cin, int(r[30])):
+                    raise ProgramError(f"op {i}: x3_src_op {src_op} names no earlier conv that writes planes buffer "
+                                       f"{x3} for this input")
         elif op == OP_DWCONV:
             n = kind_n(r[16])
             H, W, C, Ho, Wo = (int(v) for v in (r[4], r[5], r[6], r[12], r[13]))

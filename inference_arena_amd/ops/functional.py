@@ -14,7 +14,7 @@ import struct
 import numpy as np
 import torch
 
-from ..engine.planner import ACT, pack_conv_weight, pack_conv_weight_x3
+from ..engine.planner import ACT, pack_conv_weight, pack_conv_weight_x3, split_bf16x3
 from . import native
 
 IMAGE_META = struct.Struct("<qiiiiiif12x")  # must match arena::ImageMeta (48 bytes)
@@ -42,13 +42,46 @@ def pack_weights(w: torch.Tensor, b: torch.Tensor, device, dtype: str = "bf16"):
     return wt, bt, kpad, cpad, w3
 
 
+def to_x3_planes(t: torch.Tensor) -> torch.Tensor:
+    """fp32 NHWC [B, H, W, C] (C % 32 == 0) -> its x3 planes, bf16 [B, H, W, C / 32, 96]: per pixel C / 32 chunks of
+    [h 32 | m 32 | l 32], the planes of ``planner.split_bf16x3`` for 32 consecutive channels (the activation layout
+    of csrc/kernels/gemm_x3p.hip and the row format of ``pack_conv_weight_x3``)."""
+    if t.dim() != 4 or t.dtype != torch.float32 or t.shape[3] % 32:
+        raise ValueError("to_x3_planes: expects a float32 [B, H, W, C] tensor with C % 32 == 0")
+    B, H, W, C = t.shape
+    return split_bf16x3(t.reshape(B, H, W, C // 32, 32)).reshape(B, H, W, C // 32, 96)
+
+
+def from_x3_planes(p: torch.Tensor) -> torch.Tensor:
+    """x3 planes [B, H, W, C / 32, 96] (bf16, or int16 holding bf16 bits) -> fp32 [B, H, W, C] = (h + m) + l."""
+    if p.dim() != 5 or p.shape[4] != 96 or p.dtype not in (torch.bfloat16, torch.int16):
+        raise ValueError("from_x3_planes: expects a bf16 / int16 [B, H, W, C / 32, 96] tensor")
+    B, H, W, n, _ = p.shape
+    v = p.contiguous().view(torch.bfloat16).reshape(B, H, W, n, 3, 32).float()
+    return ((v[..., 0, :] + v[..., 1, :]) + v[..., 2, :]).reshape(B, H, W, n * 32)
+
+
+def _check_planes(what: str, p: torch.Tensor, shape: tuple, device) -> None:
+    if (p.dtype not in (torch.bfloat16, torch.int16) or tuple(p.shape) != shape or p.device != device
+            or not p.is_contiguous()):
+        raise ValueError(f"conv2d_nhwc: {what} must be contiguous bf16 / int16 {list(shape)} on the input's device, "
+                         f"got {p.dtype} {list(p.shape)}")
+
+
 def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, stride: int = 1, pad=None, act=None,
                 x_coff: int = 0, cin: int | None = None, out: torch.Tensor | None = None, out_coff: int = 0,
                 res: torch.Tensor | None = None, res_coff: int = 0, out2: torch.Tensor | None = None,
                 out2_coff: int = 0, f32out: bool = False, out_hw=None, bdev: torch.Tensor | None = None,
                 packed=None, impl: int = 0, pw=None, pw_out: torch.Tensor | None = None, pw_out_coff: int = 0,
-                gate=None, window=None, marks=None) -> torch.Tensor:
+                gate=None, window=None, marks=None, x_planes: bool = False,
+                out_planes: torch.Tensor | None = None, planes_only: bool = False) -> torch.Tensor:
     """NHWC conv with fused bias/act/residual/upsampled copy.
+
+    x3 planes (fp32, x3g family ``impl`` 111 + v only; csrc/kernels/gemm_x3p.hip): ``x_planes=True``: ``x`` is the
+    input's planes, bf16 / int16 [B, H, W, Cin / 32, 96] (``to_x3_planes``).  ``out_planes`` (bf16 / int16
+    [B, Ho, Wo, Cout / 32, 96]): the kernel also writes the output's planes there; the fp32 output is still
+    allocated (``out=None``), written and returned, unless ``planes_only``, which stores the planes alone and returns
+    ``out_planes``.
 
     ``window=(n_lo, n_hi)`` (x3hp kernels, impl 191 + v, only): compute and store only the output channels
     [n_lo, n_hi); the rest of ``out`` keeps its contents.  ``marks=(m, uh, uw, halo)`` (x3hp only): int32 ``m``
@@ -77,9 +110,20 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, stride: in
             not (window is None and gate is None and marks is None):
         raise ValueError("conv2d_nhwc: window, gate and marks are not x3hc options (the family runs the whole "
                          "80-channel conv on every tile)")
-    f32 = x.dtype == torch.float32
-    B, H, W, Cx = x.shape
     cout, cin_w, kh, kw = w.shape
+    if x_planes:
+        if x_coff or (cin is not None and cin != cin_w) or cin_w % 32:
+            raise ValueError("conv2d_nhwc: a planes input is one whole activation (x_coff 0, Cin % 32 == 0)")
+        if x.dim() != 5:
+            raise ValueError("conv2d_nhwc: x_planes expects x as [B, H, W, Cin / 32, 96]")
+        _check_planes("x", x, (*x.shape[:3], cin_w // 32, 96), x.device)
+        f32 = True
+        B, H, W, Cx = (*x.shape[:3], cin_w)
+    else:
+        f32 = x.dtype == torch.float32
+        B, H, W, Cx = x.shape
+    if planes_only and (out_planes is None or out is not None):
+        raise ValueError("conv2d_nhwc: planes_only needs out_planes and no out")
     cin = cin or cin_w
     if pad is None:
         pad = (kh // 2, kw // 2)
@@ -90,7 +134,11 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, stride: in
         Wo = (W + 2 * pad[1] - kw) // stride + 1
     else:
         Ho, Wo = out_hw
-    if out is None:
+    if out_planes is not None:
+        if not f32 or cout % 32:
+            raise ValueError("conv2d_nhwc: out_planes needs an fp32 conv with Cout % 32 == 0")
+        _check_planes("out_planes", out_planes, (B, Ho, Wo, cout // 32, 96), x.device)
+    if out is None and not planes_only:
         out = torch.empty(B, Ho, Wo, cout, dtype=torch.float32 if (f32out or f32) else torch.bfloat16, device=x.device)
     wt, bt, kpad, cpad, w3 = packed if packed is not None else pack_weights(w, b, x.device, "fp32" if f32 else "bf16")
     pwd = {}
@@ -144,7 +192,8 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, stride: in
     native().conv2d({
         "x": _ptr(x, x_coff), "B": B, "H": H, "W": W, "xs": Cx, "Cin": cin,
         "w": _ptr(wt), "Kpad": kpad, "bias": _ptr(bt),
-        "y": _ptr(out, out_coff), "Ho": Ho, "Wo": Wo, "ys": out.shape[-1], "Cout": cout, "Cout_pad": cpad,
+        "y": _ptr(out, out_coff), "Ho": Ho, "Wo": Wo, "ys": cout if planes_only else out.shape[-1], "Cout": cout,
+        "Cout_pad": cpad, "x_planes": int(x_planes), "y3": _ptr(out_planes),
         "KH": kh, "KW": kw, "stride": stride, "pad_t": pad[0], "pad_l": pad[1],
         "res": _ptr(res, res_coff), "rs": res.shape[-1] if res is not None else 0,
         "y2": _ptr(out2, out2_coff), "y2s": out2.shape[-1] if out2 is not None else 0,
@@ -153,7 +202,7 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, stride: in
     })
     if pw is not None:
         torch.cuda.synchronize(x.device)  # keep the packed 1x1 weights alive until the kernel ran
-    return out
+    return out_planes if planes_only else out
 
 
 def head_mark(logits: torch.Tensor, coff: int, n: int, gate_min: float, marks: torch.Tensor | None = None,

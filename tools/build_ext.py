@@ -32,6 +32,7 @@ SOURCES = [
     "kernels/conv_mfma.hip",
     "kernels/conv_f32.hip",
     "kernels/gemm_x3.hip",
+    "kernels/gemm_x3p.hip",
     "kernels/halo_x3g.hip",
     "kernels/halo_x3p.hip",
     "kernels/halo_x3c.hip",
@@ -85,7 +86,9 @@ SOURCES = [
 # a kernel's split form changes only with a measurement).  The host pass takes the feature switch without effect.
 # ir_group_x3.hip, new as well, is built the same way for the same reason: 228 / 253 / 252 VGPRs and no scratch in its
 # three instantiations; with packed ops 228 / 256 / 252 and 16 bytes of scratch a lane in <4, 10>.
+# gemm_x3p.hip, new as well, likewise: its planes store splits with the two-at-a-time form.
 PER_FILE_FLAGS: dict[str, list[str]] = {
+    "gemm_x3p.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "halo_x3c.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "ir_group_x3.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
