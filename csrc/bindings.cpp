@@ -225,6 +225,32 @@ void py_c3_block(const py::dict& d) {
     c3_fused(p, stream_of(d));
 }
 
+// one fused fp32 C3 bottleneck (c3_bneck_x3.hip); returns the slices launched
+int py_c3_bneck_x3(const py::dict& d) {
+  BneckParams p{};
+  p.x = ptr<const float*>(d, "x");
+  p.xs = req<int>(d, "xs");
+  p.x_coff = get<int>(d, "x_coff", 0);
+  p.y = ptr<float*>(d, "y");
+  p.ys = req<int>(d, "ys");
+  p.y_coff = get<int>(d, "y_coff", 0);
+  p.B = req<int>(d, "B");
+  p.H = req<int>(d, "H");
+  p.W = req<int>(d, "W");
+  p.C = req<int>(d, "C");
+  p.res = req<int>(d, "res");
+  p.w1 = ptr<const void*>(d, "w1");
+  p.b1 = ptr<const float*>(d, "b1");
+  p.w2 = ptr<const void*>(d, "w2");
+  p.b2 = ptr<const float*>(d, "b2");
+  p.bdev = ptr<const int*>(d, "bdev");
+  p.sk_ws = ptr<float*>(d, "sk_ws");
+  p.sk_ws_bytes = get<int64_t>(d, "sk_ws_bytes", 0);
+  p.slices = get<int>(d, "slices", 0);
+  prepare_kernels();
+  return c3_bneck_x3(p, stream_of(d));
+}
+
 void py_sppf(const py::dict& d) {
   SppfParams p{};
   p.buf = ptr<void*>(d, "buf");
@@ -723,6 +749,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("sppf_pool", &py_sppf);
   m.def("ir_block", &py_ir_block);
   m.def("c3_block", &py_c3_block);
+  m.def("c3_bneck_x3", &py_c3_bneck_x3);
+  m.def("c3_bneck_x3_supported", &c3_bneck_x3_supported, py::arg("C"), py::arg("B"), py::arg("H"), py::arg("W"),
+        py::arg("xs"), py::arg("x_coff"), py::arg("ys"), py::arg("y_coff"));
   m.def("set_conv_pw", &set_conv_pw);
   m.def("set_conv_v3", &set_conv_v3);
   m.def("set_ir_wave", &set_ir_wave);

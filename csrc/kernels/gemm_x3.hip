@@ -343,6 +343,11 @@ __global__ __launch_bounds__(256) void x3g_sk_reduce_kernel(const ConvParams p) 
   }
 }
 
+void x3g_sk_reduce(const ConvParams& p, hipStream_t s) {
+  const long items = (long)p.B * p.Ho * p.Wo * (p.Cout / 4);
+  hipLaunchKernelGGL(x3g_sk_reduce_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p);
+}
+
 namespace {
 
 template <int WM, int WN, int TM, int TN, bool IL>
@@ -369,8 +374,7 @@ bool xg_launch_sk(const ConvParams& p, hipStream_t s, int splits) {
   q.sk_splits = splits;
   hipLaunchKernelGGL((conv_x3g_kernel<WM, WN, TM, TN, false, true>), dim3((unsigned)(tiles * splits)),
                      dim3(WM * WN * 64), xg_lds_bytes(BM, BN), s, q);
-  const long items = M * (p.Cout / 4);
-  hipLaunchKernelGGL(x3g_sk_reduce_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, q);
+  x3g_sk_reduce(q, s);
   return true;
 }
 

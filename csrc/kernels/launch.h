@@ -108,6 +108,9 @@ bool x3g_supported(const ConvParams& p);
 bool conv_x3g(const ConvParams& p, hipStream_t s, int v);
 bool conv_x3g_sk(const ConvParams& p, hipStream_t s, int v);  // runs the tile unsplit where sk_ws cannot hold the conv
 void x3g_prepare();
+// the split-K second pass of conv_x3g_sk on its own: y = act(sum over sk_splits partial tiles in sk_ws + bias) (+ res)
+// from B, Ho, Wo, Cout, Cout_pad, bias, act, res / rs, y / ys, y2 / y2s, bdev, sk_ws, sk_splits
+void x3g_sk_reduce(const ConvParams& p, hipStream_t s);
 // x3gp (gemm_x3p.hip): tile v (XG_VARIANTS 0..9; v + 10 is the same tile) of the x3g GEMM reading and / or writing
 // x3 planes (ConvParams.x_planes, y3); throws std::runtime_error naming what it does not take
 void conv_x3gp(const ConvParams& p, hipStream_t s, int v);
@@ -264,6 +267,34 @@ bool c3_x3_supported(int C1, int CH, int NB, bool res, int H, int W);
 void c3_x3(const C3Params& p, hipStream_t s);
 void c3_x3_prepare();
 void c3_fused(const C3Params& p, hipStream_t s);
+
+// ---------------------------------------------------------------- fused C3 bottleneck, fp32 (c3_bneck_x3.hip)
+// y = silu(conv3x3_p1(silu(x W1 + b1), W2) + b2) [+ x] over fp32 NHWC channel slices of c_ = C channels (32, 64 or
+// 128), any H, W >= 1; the 1x1's output only exists in LDS.  Weights are the pre-split planes of the two convs as
+// the planner packs them for the x3 kernels (pack_conv_weight_x3: w1 [C / 32][C][192 B], w2 [9 C / 32][C][192 B]).
+struct BneckParams {
+  const float* x;  // source buffer; the slice is channels [x_coff, x_coff + C) at pixel stride xs
+  int xs, x_coff;
+  float* y;        // destination buffer, likewise; must not overlap the source slice
+  int ys, y_coff;
+  int B, H, W, C;
+  int res;         // add the source (the Bottleneck's shortcut)
+  const void* w1;
+  const float* b1;  // fp32 [C]
+  const void* w2;
+  const float* b2;  // fp32 [C]
+  const int* bdev;  // optional live batch count on device
+  // split-K workspace for the partial tiles of a sliced launch (slices x B x H x W x C fp32; ConvParams::sk_ws)
+  float* sk_ws;
+  int64_t sk_ws_bytes;
+  int slices;  // mid-channel slices (workgroups per pixel tile), at most C / 32; 0: c3_bneck_x3_slices
+};
+bool c3_bneck_x3_supported(int C, int B, int H, int W, int xs, int x_coff, int ys, int y_coff);
+int c3_bneck_x3_slices(int C, int B, int H, int W);  // the launcher's rule: 1 once B x tiles fill the device
+// -> the slices launched; throws std::invalid_argument for an unsupported geometry, overlapping slices or forced
+// slices the workspace cannot hold
+int c3_bneck_x3(const BneckParams& p, hipStream_t s);
+void c3_bneck_x3_prepare();
 
 // ---------------------------------------------------------------- SPPF pools (K5)
 // x: [B,H,W] channels [0,C) of a buffer with pixel stride xs; writes the

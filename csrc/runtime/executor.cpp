@@ -959,6 +959,30 @@ void Executor::enqueue_program(const std::vector<OpRecord>& prog, Bucket& bk, Sl
           c3_fused(p, s);
         break;
       }
+      case OP_C3BNECK: {
+        if (!f32) throw std::runtime_error("executor: the fused bottleneck is an fp32 op");
+        BneckParams p{};
+        p.x = (const float*)resolve(bk, sl, r[1], 0, eb);  // the launcher takes buffer + channel offset
+        p.x_coff = (int)r[2];
+        p.xs = (int)r[3];
+        p.H = (int)r[4];
+        p.W = (int)r[5];
+        p.C = (int)r[6];
+        p.res = (int)r[7];
+        p.w1 = W + r[8];
+        p.b1 = (const float*)(W + r[9]);
+        p.w2 = W + r[10];
+        p.b2 = (const float*)(W + r[11]);
+        p.y = (float*)resolve(bk, sl, r[12], 0, eb);
+        p.y_coff = (int)r[13];
+        p.ys = (int)r[14];
+        p.B = batch(r[15]);
+        p.bdev = bdev(r[15]);
+        p.sk_ws = sl.sk_ws;  // the slot's split-K workspace: sliced launches below a full grid
+        p.sk_ws_bytes = sk_ws_bytes();
+        c3_bneck_x3(p, s);
+        break;
+      }
       case OP_STEMFUSED: {
         StemFusedParams p{};
         p.src = (int)r[1];

@@ -88,6 +88,7 @@ enum OpType : int64_t {
   OP_C3FUSED = 16,
   OP_HEADPOOL = 17,
   OP_STAMP = 18,  // 1: stamp index (0 program start, 1 classifier start, 2 end): device wall clock -> results
+  OP_C3BNECK = 19,  // fp32 C3 Bottleneck as one kernel (planner.py C3BNECK row; kernels/c3_bneck_x3.hip)
 };
 
 // Reserved buffer ids (the planner's arena buffers are ids >= 0).

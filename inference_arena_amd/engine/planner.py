@@ -61,6 +61,10 @@ Op record layouts (index: field) — keep in sync with executor.cpp:
            (MobileNetV2 head 1x1 conv + activation + global average pool, csrc/kernels/head_pool.hip)
   STAMP    1 index (0 program start, 1 classifier start, 2 end): the device wall clock into the results
            (per-batch detection / classification device time; executor BatchResult det_ms / cls_ms)
+  C3BNECK  1 x_buf 2 x_coff 3 x_cs 4 H 5 W 6 C 7 res 8 w1_off 9 b1_off 10 w2_off 11 b2_off 12 y_buf 13 y_coff 14 y_cs
+           15 batch_kind
+           (fp32 C3 Bottleneck, 1x1 -> 3x3 (+ shortcut), as one kernel, csrc/kernels/c3_bneck_x3.hip; w1 / w2: the
+            pre-split planes of the two convs, pack_conv_weight_x3; ARENA_C3_BNECK)
 
 Every record: field 47 (``OP_DTYPE_FIELD``) = activation precision of the op, 0 = bf16 activations and
 weights with fp32 accumulation (the tuned fused kernels), 1 = exact fp32 (fp32 activations and weights,
@@ -84,6 +88,8 @@ OP_DTYPE_FIELD = 47
 DTYPES = ("bf16", "fp32")
 (OP_CONV, OP_DWCONV, OP_SPPF, OP_LETTERBOX, OP_ZERO, OP_DECODE, OP_NMS, OP_CROPPLAN, OP_CROPGATHER, OP_AVGPOOL,
  OP_TOPK, OP_TENSORIN, OP_YOLORAW, OP_IRBLOCK, OP_STEMFUSED, OP_C3FUSED, OP_HEADPOOL, OP_STAMP) = range(1, 19)
+OP_C3BNECK = 19
+C3_BNECK_CH = (32, 64, 128)  # c_ of csrc/kernels/c3_bneck_x3.hip's instantiations
 BUF_NONE, BUF_CTRL, BUF_META, BUF_POOL, BUF_DET, BUF_DETCOUNT, BUF_TOPK, BUF_RAWOUT = -1, -10, -11, -12, -13, -14, -15, -16
 BUF_XCROPS = -17  # crop plan exported to a second-stage executor (split topology; executor.h)
 
@@ -290,6 +296,14 @@ def x3_planes_enabled() -> bool:
     activation as x3 planes (OP_CONV fields 42-44); the executor then runs producer and consumer on the x3gp kernels
     (csrc/kernels/gemm_x3p.hip) where both are tuned to the x3g family.  Off: programs are unchanged."""
     return os.environ.get("ARENA_X3_PLANES", "0").lower() not in ("0", "false", "no", "off", "")
+
+
+def c3_bneck_enabled() -> bool:
+    """``ARENA_C3_BNECK`` (default 0): fp32 programs run each Bottleneck of the unfused C3 blocks (1x1 -> 3x3 +
+    shortcut, c_ 32 / 64 / 128) as one op (OP_C3BNECK, csrc/kernels/c3_bneck_x3.hip) instead of two convs; the
+    block's working buffer gets a third c_-wide slot so that no bottleneck writes what it reads.  Off: programs are
+    unchanged."""
+    return os.environ.get("ARENA_C3_BNECK", "0").lower() not in ("0", "false", "no", "off", "")
 
 
 def ir_crop_f32_policy() -> str:
@@ -692,6 +706,24 @@ class ProgramBuilder:
         wd, bd, _, _ = pack_conv_weight(w3, b3)
         rec += [self.weights.add(wd), self.weights.add(bd), dst.bid, dst.coff, dst.cs, kind]
         self._emit(rec, src, dst)
+
+    def c3_bneck(self, src: View, dst: View, H: int, W: int, pw: tuple, conv3: tuple, res: bool,
+                 kind: int = IMAGES) -> None:
+        """A C3 Bottleneck as one op (fp32 programs): ``dst`` = SiLU(conv3x3(SiLU(conv1x1(``src``)))) (+ ``src``),
+        ``pw`` = (w1 [c_, c_, 1, 1], b1), ``conv3`` = (w2 [c_, c_, 3, 3], b2), BN folded; c_ 32, 64 or 128.  Every
+        workgroup reads its neighbours' pixels, so ``dst`` must not overlap ``src``."""
+        if not self.f32:
+            raise ValueError("c3_bneck: fp32 programs only (csrc/kernels/c3_bneck_x3.hip)")
+        (w1, b1), (w2, b2) = pw, conv3
+        c = src.C
+        if c not in C3_BNECK_CH or dst.C != c or tuple(w1.shape) != (c, c, 1, 1) or tuple(w2.shape) != (c, c, 3, 3):
+            raise ValueError(f"c3_bneck: needs c_ in {C3_BNECK_CH} with [c_, c_, 1, 1] and [c_, c_, 3, 3] weights")
+        if src.bid == dst.bid and src.coff < dst.coff + c and dst.coff < src.coff + c:
+            raise ValueError("c3_bneck: the destination view overlaps the source view")
+        offs = [self.weights.add(pack_conv_weight_x3(w1)), self.weights.add(f32_bytes(b1)),
+                self.weights.add(pack_conv_weight_x3(w2)), self.weights.add(f32_bytes(b2))]
+        self._emit([OP_C3BNECK, src.bid, src.coff, src.cs, H, W, c, int(res), *offs, dst.bid, dst.coff, dst.cs, kind],
+                   src, dst)
 
     def stem_fused(self, dst: View, w: torch.Tensor, b: torch.Tensor, *, S: int, act: str, crops: Buffer | None = None,
                    mean=None, std=None, kind: int = IMAGES, second: tuple | None = None,

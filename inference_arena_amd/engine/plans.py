@@ -37,7 +37,8 @@ import torch
 from ..models.common import fold, fold_conv_bn
 from ..models.mobilenetv2 import MobileNetV2
 from ..models.yolov5nu import STRIDES, YOLOv5nu
-from .planner import BUF_NONE, BUF_RAWOUT, BUF_XCROPS, CROPS, IMAGES, Program, ProgramBuilder, Reserved, View
+from .planner import (BUF_NONE, BUF_RAWOUT, BUF_XCROPS, C3_BNECK_CH, CROPS, IMAGES, Program, ProgramBuilder, Reserved, View,
+                      c3_bneck_enabled)
 
 CAND_BYTES = 32
 CROPREF_BYTES = 32
@@ -105,10 +106,26 @@ def _c3(pb: ProgramBuilder, m, src: View, dst: View, H: int, W: int, name: str) 
         pb.c3_fused(src, dst, H, W, (torch.cat([w1, w2]), torch.cat([b1, b2])),
                     [(fold(bn.cv1), fold(bn.cv2)) for bn in m.m], fold(m.cv3), res=res)
         return
-    T = pb.tensor(f"{name}.T", H, W, 2 * c_)
-    U = pb.tensor(f"{name}.U", H, W, c_)
     w1, b1 = fold(m.cv1)
     w2, b2 = fold(m.cv2)
+    if pb.f32 and c3_bneck_enabled() and c_ in C3_BNECK_CH:
+        # each Bottleneck as one op (csrc/kernels/c3_bneck_x3.hip).  T = [x | y2 | u]: bottleneck i reads slot 0 or
+        # 2 and writes the other, so that no launch writes what a neighbouring tile still reads; U disappears
+        T = pb.tensor(f"{name}.T", H, W, 3 * c_)
+        pb.conv(src, View(T, 0, 2 * c_), torch.cat([w1, w2]), torch.cat([b1, b2]))
+        cur = 0
+        for bn in m.m:
+            pb.c3_bneck(View(T, cur * c_, c_), View(T, (2 - cur) * c_, c_), H, W, fold(bn.cv1), fold(bn.cv2),
+                        res=bool(bn.add))
+            cur = 2 - cur
+        w3, b3 = fold(m.cv3)
+        if cur == 0:
+            pb.conv(View(T, 0, 2 * c_), dst, w3, b3)
+        else:  # the chain's output is in slot 2: cv3 reads [y2 | u], its input-channel halves swapped to match
+            pb.conv(View(T, c_, 2 * c_), dst, torch.cat([w3[:, c_:], w3[:, :c_]], 1), b3)
+        return
+    T = pb.tensor(f"{name}.T", H, W, 2 * c_)
+    U = pb.tensor(f"{name}.U", H, W, c_)
     pb.conv(src, View(T, 0, 2 * c_), torch.cat([w1, w2]), torch.cat([b1, b2]))
     for bn in m.m:
         wa, ba = fold(bn.cv1)

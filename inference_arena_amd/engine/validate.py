@@ -17,8 +17,10 @@ from ..engine.planner import (
     BUF_RAWOUT,
     BUF_TOPK,
     BUF_XCROPS,
+    C3_BNECK_CH,
     CROPS,
     OP_AVGPOOL,
+    OP_C3BNECK,
     OP_C3FUSED,
     OP_HEADPOOL,
     OP_CONV,
@@ -290,6 +292,24 @@ def validate_program(prog: Program, B: int, crop_cap: int, *, max_det: int, cand
                 weights(i, int(r[15 + 4 * k]), CH * 4, f"c3 bottleneck {k} cv2 bias")
             weights(i, int(r[20]), 4 * CH * CH * 2, "c3 cv3 weight")
             weights(i, int(r[21]), 2 * CH * 4, "c3 cv3 bias")
+        elif op == OP_C3BNECK:  # csrc/kernels/c3_bneck_x3.hip (mirror of arena::c3_bneck_x3's checks)
+            n = kind_n(r[15])
+            H, W, C = int(r[4]), int(r[5]), int(r[6])
+            if not f32 or C not in C3_BNECK_CH or H < 1 or W < 1 or int(r[7]) not in (0, 1):
+                raise ProgramError(f"op {i}: unsupported fused bottleneck (fp32 {f32}, c_ {C}, {H} x {W})")
+            xc, xs, yc, ys = int(r[2]), int(r[3]), int(r[13]), int(r[14])
+            if xc % 4 or xs % 4 or yc % 4 or ys % 4 or n * H * W * max(xs, ys) * 4 >= 2 ** 31 - 2 ** 20:
+                raise ProgramError(f"op {i}: fused bottleneck views must be 4-aligned channel slices of maps < 2 GiB")
+            view(i, r[1], xc, xs, n * H * W, C, el, "bottleneck input")
+            view(i, r[12], yc, ys, n * H * W, C, el, "bottleneck output")
+            # every tile reads its neighbours' pixels: the destination must not be the source's channels
+            if int(r[1]) == int(r[12]) and xc < yc + C and yc < xc + C:
+                raise ProgramError(f"op {i}: fused bottleneck output [{yc}, {yc + C}) overlaps its input "
+                                   f"[{xc}, {xc + C}) of {names.get(int(r[1]), int(r[1]))}")
+            weights(i, int(r[8]), (C // 32) * C * 192, "bottleneck 1x1 x3 weight")
+            weights(i, int(r[9]), C * 4, "bottleneck 1x1 bias")
+            weights(i, int(r[10]), 9 * (C // 32) * C * 192, "bottleneck 3x3 x3 weight")
+            weights(i, int(r[11]), C * 4, "bottleneck 3x3 bias")
         elif op == OP_STEMFUSED:
             src, S, kpad, cout, kind, ks = int(r[1]), int(r[5]), int(r[7]), int(r[9]), int(r[18]), int(r[19])
             n = kind_n(kind)

@@ -316,6 +316,52 @@ def c3_x3_nhwc(x: torch.Tensor, cv12, bottleneck, cv3) -> torch.Tensor:
     return y
 
 
+def c3_bottleneck_nhwc(x: torch.Tensor, pw, conv3, *, shortcut: bool, x_coff: int = 0, c: int | None = None,
+                       out: torch.Tensor | None = None, out_coff: int = 0, bdev: torch.Tensor | None = None,
+                       slices: int = 0) -> torch.Tensor:
+    """fp32 YOLOv5 Bottleneck as one kernel (csrc/kernels/c3_bneck_x3.hip): SiLU(conv3x3(SiLU(conv1x1(x)))) [+ x]
+    over c_ = 32, 64 or 128 channels of a map of any size; the 1x1's output only exists in LDS.  ``pw`` = (w1 [c_,
+    c_, 1, 1], b1), ``conv3`` = (w2 [c_, c_, 3, 3], b2), BN folded.  Reads channels [x_coff, x_coff + c_) of the
+    float32 [B, H, W, Cx] ``x``; ``out``: a contiguous float32 [B, H, W, >= out_coff + c_] tensor to write channels
+    [out_coff, out_coff + c_) of (everything else is left as it is) instead of a fresh one.  The written slice must
+    not overlap the slice read (every tile reads its neighbours' pixels).  ``bdev``: live image count on the device.
+    ``slices``: mid-channel slices per pixel tile (1 .. c_ / 32; more than one runs the split-K form: partial tiles
+    into a workspace, then the deterministic reduce); 0: the launcher's rule (one slice once B x tiles fill the
+    device).  ValueError for another c_, a non-float32 ``x`` or an overlapping ``out``."""
+    (w1, b1), (w2, b2) = pw, conv3
+    ch = w1.shape[0]
+    c = c or ch
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("c3_bottleneck_nhwc: x must be contiguous float32 [B, H, W, C]")
+    B, H, W, Cx = x.shape
+    if c != ch or tuple(w1.shape) != (ch, ch, 1, 1) or tuple(w2.shape) != (ch, ch, 3, 3):
+        raise ValueError("c3_bottleneck_nhwc: weights must be [c_, c_, 1, 1] and [c_, c_, 3, 3]")
+    if out is None:
+        out, out_coff = torch.empty(B, H, W, ch, dtype=torch.float32, device=x.device), 0
+    if (out.dim() != 4 or out.shape[:3] != (B, H, W) or out.dtype != torch.float32 or out.device != x.device
+            or not out.is_contiguous()):
+        raise ValueError(f"c3_bottleneck_nhwc: out {tuple(out.shape)} {out.dtype} does not fit the block's output")
+    if not native().c3_bneck_x3_supported(ch, B, H, W, Cx, x_coff, out.shape[3], out_coff):
+        raise ValueError("c3_bottleneck_nhwc: c_ must be 32, 64 or 128 over 4-aligned channel slices inside x / out")
+    if not 0 <= slices <= ch // 32:
+        raise ValueError(f"c3_bottleneck_nhwc: slices must be 0 (auto) .. {ch // 32}")
+    if out.data_ptr() == x.data_ptr() and x_coff < out_coff + ch and out_coff < x_coff + ch:
+        raise ValueError("c3_bottleneck_nhwc: out's channels overlap the channels read from x")
+    dev = [torch.frombuffer(bytearray(pack_conv_weight_x3(w.detach().cpu().float())), dtype=torch.int16).to(x.device)
+           for w in (w1, w2)]
+    dev += [b.detach().float().contiguous().to(x.device) for b in (b1, b2)]
+    ws = torch.empty(max(1, ch // 32) * B * H * W * ch, dtype=torch.float32, device=x.device)
+    try:
+        native().c3_bneck_x3({"x": _ptr(x), "xs": Cx, "x_coff": x_coff, "y": _ptr(out), "ys": out.shape[3],
+                              "y_coff": out_coff, "B": B, "H": H, "W": W, "C": ch, "res": int(shortcut),
+                              "w1": _ptr(dev[0]), "w2": _ptr(dev[1]), "b1": _ptr(dev[2]), "b2": _ptr(dev[3]),
+                              "bdev": _ptr(bdev), "sk_ws": _ptr(ws), "sk_ws_bytes": ws.numel() * 4,
+                              "slices": int(slices), "stream": _stream()})
+    finally:
+        torch.cuda.synchronize(x.device)  # keep the packed weights and the workspace alive until the kernels ran
+    return out
+
+
 def c3_fused_nhwc(x: torch.Tensor, cv12, bottleneck, cv3, *, n: int = 1, shortcut: bool = True, x_coff: int = 0,
                   c1: int | None = None, out: torch.Tensor | None = None, out_coff: int = 0,
                   bdev: torch.Tensor | None = None) -> torch.Tensor:

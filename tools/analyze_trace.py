@@ -27,7 +27,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 
 KIND = {1: "conv", 2: "dwconv", 3: "sppf", 4: "letterbox", 5: "zero", 6: "decode", 7: "nms", 8: "cropplan",
         9: "cropgather", 10: "avgpool", 11: "topk", 12: "tensorin", 13: "yoloraw", 14: "irblock", 15: "stemfused", 16: "c3fused",
-        17: "headpool", 18: "stamp"}
+        17: "headpool", 18: "stamp", 19: "c3bneck"}
 FIRST_KERNEL = {4: "letterbox", 12: "tensor_in", 15: "stem_fused", 18: "stamp_kernel"}
 
 
@@ -42,6 +42,8 @@ def describe(rec) -> str:
     if t == 16:
         return (f"c3 {int(rec[4])}x{int(rec[5])}x{int(rec[6])} c_={int(rec[7])} n={int(rec[8])}"
                 f"{' res' if rec[9] else ''}")
+    if t == 19:
+        return f"bneck {int(rec[4])}x{int(rec[5])}x{int(rec[6])} 1x1 -> k3{' res' if rec[7] else ''}"
     if t == 15:
         src = {0: "letterbox", 1: "crop gather", 2: "tensor"}.get(int(rec[1]), "?")
         d = f"{src} + stem k{int(rec[19])} -> {int(rec[9])}"

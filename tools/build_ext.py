@@ -52,6 +52,7 @@ SOURCES = [
     "kernels/conv3x3_v3.hip",
     "kernels/c3_fused.hip",
     "kernels/c3_x3.hip",
+    "kernels/c3_bneck_x3.hip",
     "kernels/preprocess.hip",
     "kernels/stem_fused.hip",
     "kernels/detect.hip",
@@ -87,7 +88,10 @@ SOURCES = [
 # ir_group_x3.hip, new as well, is built the same way for the same reason: 228 / 253 / 252 VGPRs and no scratch in its
 # three instantiations; with packed ops 228 / 256 / 252 and 16 bytes of scratch a lane in <4, 10>.
 # gemm_x3p.hip, new as well, likewise: its planes store splits with the two-at-a-time form.
+# c3_bneck_x3.hip, new as well, likewise (both of its splits use the two-at-a-time form): 106 / 118 / 122 VGPRs + 24 / 44 /
+# 76 AGPRs and no scratch for c_ = 32 / 64 / 128, so register pressure asks for nothing either way.
 PER_FILE_FLAGS: dict[str, list[str]] = {
+    "c3_bneck_x3.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "gemm_x3p.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "halo_x3c.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "ir_group_x3.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
