@@ -1561,6 +1561,10 @@ void conv2d_f32(const ConvParams& p, hipStream_t s) {
     conv_x3gp(p, s, p.impl - kF32X3G);
     return;
   }
+  if (p.pw_w != nullptr && p.stride == 2) {  // downsampling conv + the next block's 1x1: x3ds (down_x3.hip)
+    conv_down_x3(p, s);
+    return;
+  }
   if (p.pw_w != nullptr) {  // fused Detect-head 1x1: the x3hg / x3hr epilogue variants and x3hc implement it
     if (f32_conv_impl_in(p.impl, F32Family::X3HC)) {
       if (!conv_x3hc(p, s, p.impl - kF32X3HC)) throw std::runtime_error(f32_family(F32Family::X3HC).reject);

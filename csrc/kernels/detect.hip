@@ -314,6 +314,7 @@ void prepare_kernels() {
   x3gp_prepare();
   c3_x3_prepare();
   c3_bneck_x3_prepare();
+  down_x3_prepare();
   x3hg_prepare();
   x3hp_prepare();
   x3hc_prepare();

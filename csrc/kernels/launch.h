@@ -126,6 +126,15 @@ void x3hp_prepare();
 bool x3hc_supported(const ConvParams& p);
 bool conv_x3hc(const ConvParams& p, hipStream_t s, int v);
 void x3hc_prepare();
+// x3ds (down_x3.hip): 3x3 stride-2 pad-1 conv + SiLU with the fused 1x1 C -> C + SiLU, (Cin, C) = (32, 64), (64, 128),
+// (128, 256); an impl kF32X3HGPw + v with v < down_x3_variants() names the tile, any other impl lets down_x3_tile
+// choose.  Throws std::invalid_argument for a conv it does not take and for a destination that overlaps the source;
+// returns the tile variant launched.
+bool down_x3_supported(const ConvParams& p);
+int down_x3_variants();
+int down_x3_tile(int B, int Ho, int Wo);
+int conv_down_x3(const ConvParams& p, hipStream_t s);
+void down_x3_prepare();
 // fused-1x1 x3hg variant (halo_x3g.hip HG_PW_VARIANTS) that conv2d_f32 runs for ConvParams.impl on a conv with
 // cout_pad padded output channels (kF32X3HGPw + v, kF32X3HGPwSmall + v, 0 = by channel count), -1: none; and its
 // pixel tile

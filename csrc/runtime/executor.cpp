@@ -363,6 +363,10 @@ void Executor::add_bucket(int B, const int64_t* offsets, int n_buffers, int64_t 
       const bool f32 = prog_[i][kDtypeField] == 1;
       const bool ok = f32 ? f32_conv_impl_valid(v) : v >= 0 && v <= 3;
       if (!ok || (v != 0 && prog_[i][0] != OP_CONV)) throw std::runtime_error("add_bucket: bad tuning entry");
+      // a stride-2 conv with a fused 1x1 is x3ds (kernels/down_x3.hip): the launcher's rule, or one of its tiles
+      if (f32 && prog_[i][0] == OP_CONV && prog_[i][34] > 0 && prog_[i][19] == 2 && v != 0 &&
+          !(f32_conv_impl_in(v, F32Family::X3HGPw) && v - kF32X3HGPw < down_x3_variants()))
+        throw std::runtime_error("add_bucket: bad tuning entry for a stride-2 conv with a fused 1x1");
       bk.impl[i] = (int16_t)v;
     }
   } else if (autotune_) {
@@ -409,6 +413,10 @@ void Executor::autotune(Bucket& bk) {
     }
     if (!f32 && prog_[i][34] > 0) {  // fused pointwise epilogue: only the v3 halo-tile kernel implements it
       bk.impl[i] = 2;
+      continue;
+    }
+    if (f32 && prog_[i][34] > 0 && prog_[i][19] == 2) {  // x3ds: one kernel, its launcher picks the tile; not timed
+      bk.impl[i] = 0;
       continue;
     }
     const int reps = f32 ? 5 : 3;
@@ -709,7 +717,7 @@ void Executor::enqueue_program(const std::vector<OpRecord>& prog, Bucket& bk, Sl
           p.lb_meta = meta;
           p.impl = kF32X3H16;
         }
-        if (r[34] > 0) {  // fused pointwise epilogue (Detect head 3x3 -> 1x1)
+        if (r[34] > 0) {  // fused pointwise epilogue (Detect head 3x3 -> 1x1; stride 2: x3ds, backbone 3x3 s2 -> 1x1)
           p.pw_w = W + r[31];
           p.pw_kpad = (int)r[32];
           p.pw_bias = (const float*)(W + r[33]);

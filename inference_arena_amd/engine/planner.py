@@ -89,6 +89,7 @@ DTYPES = ("bf16", "fp32")
 (OP_CONV, OP_DWCONV, OP_SPPF, OP_LETTERBOX, OP_ZERO, OP_DECODE, OP_NMS, OP_CROPPLAN, OP_CROPGATHER, OP_AVGPOOL,
  OP_TOPK, OP_TENSORIN, OP_YOLORAW, OP_IRBLOCK, OP_STEMFUSED, OP_C3FUSED, OP_HEADPOOL, OP_STAMP) = range(1, 19)
 OP_C3BNECK = 19
+DOWN_PW_CH = ((32, 64, 64), (64, 128, 128), (128, 256, 256))  # (Cin, C, C2) of csrc/kernels/down_x3.hip
 C3_BNECK_CH = (32, 64, 128)  # c_ of csrc/kernels/c3_bneck_x3.hip's instantiations
 BUF_NONE, BUF_CTRL, BUF_META, BUF_POOL, BUF_DET, BUF_DETCOUNT, BUF_TOPK, BUF_RAWOUT = -1, -10, -11, -12, -13, -14, -15, -16
 BUF_XCROPS = -17  # crop plan exported to a second-stage executor (split topology; executor.h)
@@ -306,6 +307,14 @@ def c3_bneck_enabled() -> bool:
     return os.environ.get("ARENA_C3_BNECK", "0").lower() not in ("0", "false", "no", "off", "")
 
 
+def down_pw_enabled() -> bool:
+    """``ARENA_DOWN_PW`` (default 0): fp32 programs run each backbone downsampling conv (3x3 stride 2, 32 -> 64,
+    64 -> 128, 128 -> 256) together with the merged cv1|cv2 1x1 of the C3 block it feeds as one stride-2 conv record
+    with a fused 1x1 (csrc/kernels/down_x3.hip); the map between the two is not allocated.  Off: programs are
+    unchanged."""
+    return os.environ.get("ARENA_DOWN_PW", "0").lower() not in ("0", "false", "no", "off", "")
+
+
 def ir_crop_f32_policy() -> str:
     """``ARENA_IRC_F32``: ``auto`` (default), ``all``/``1`` or ``none``/``0`` — which fp32 MobileNetV2 14x14 / 7x7
     blocks run as the fused x3 kernel (csrc/kernels/ir_crop_f32.hip).  ``auto`` takes the stride-1 14x14 blocks,
@@ -495,8 +504,11 @@ class ProgramBuilder:
             if ci2 != cout or w2.shape[2:] != (1, 1) or co2 != pw_dst.C:
                 raise ValueError("conv: fused pointwise weights must be [C2, Cout, 1, 1] with C2 == pw dst C")
             if self.f32:  # x3hg epilogue: pre-split 1x1 planes, the 3x3 itself as x3g planes (fields 40-41)
-                if (kh, kw, stride) != (3, 3, 1):
-                    raise ValueError("conv: the fp32 fused pointwise epilogue needs a 3x3 stride-1 conv")
+                if (kh, kw, stride) != (3, 3, 1) and not (
+                        (kh, kw, stride, pad) == (3, 3, 2, (1, 1)) and (cin, cout, co2) in DOWN_PW_CH
+                        and act == "silu" and act2 == "silu" and res is None and dst2 is None):
+                    raise ValueError("conv: the fp32 fused pointwise epilogue needs a 3x3 stride-1 conv, or a stride-2 "
+                                     "pad-1 one that csrc/kernels/down_x3.hip takes")
                 kpad2, cpad2 = _round(cout, 32), _round(co2, 16)
                 wb2 = pack_pw_weight_x3(w2, kpad2)
                 bb2 = torch.zeros(cpad2)

@@ -37,8 +37,8 @@ import torch
 from ..models.common import fold, fold_conv_bn
 from ..models.mobilenetv2 import MobileNetV2
 from ..models.yolov5nu import STRIDES, YOLOv5nu
-from .planner import (BUF_NONE, BUF_RAWOUT, BUF_XCROPS, C3_BNECK_CH, CROPS, IMAGES, Program, ProgramBuilder, Reserved, View,
-                      c3_bneck_enabled)
+from .planner import (BUF_NONE, BUF_RAWOUT, BUF_XCROPS, C3_BNECK_CH, CROPS, DOWN_PW_CH, IMAGES, Program, ProgramBuilder,
+                      Reserved, View, c3_bneck_enabled, down_pw_enabled)
 
 CAND_BYTES = 32
 CROPREF_BYTES = 32
@@ -91,7 +91,17 @@ def fuse_c3_f32() -> bool:
     return os.environ.get("ARENA_FUSE_C3_F32", "1").lower() not in ("0", "false", "no", "off")
 
 
-def _c3(pb: ProgramBuilder, m, src: View, dst: View, H: int, W: int, name: str) -> None:
+def _down_pw(pb: ProgramBuilder, down, m, src: View) -> bool:
+    """ARENA_DOWN_PW: does the stride-2 3x3 ``down`` over ``src``, read only by the C3 block ``m``, run fused with
+    ``m``'s merged cv1|cv2 1x1 (csrc/kernels/down_x3.hip)?"""
+    w = down.conv.weight
+    return (pb.f32 and down_pw_enabled() and tuple(w.shape[2:]) == (3, 3) and tuple(down.conv.stride) == (2, 2)
+            and (src.C, w.shape[0], 2 * m.c_) in DOWN_PW_CH)
+
+
+def _c3(pb: ProgramBuilder, m, src: View | None, dst: View, H: int, W: int, name: str, down: tuple | None = None) -> None:
+    """``down=(src view, (H, W) of it, (w, b))``: the block's input is that stride-2 conv's output, which is not stored:
+    the block's first op is the conv with cv1|cv2 fused into it (``_down_pw``), and ``src`` is None."""
     c_ = m.c_
     res = bool(m.m[0].add)
     if pb.f32:
@@ -99,7 +109,7 @@ def _c3(pb: ProgramBuilder, m, src: View, dst: View, H: int, W: int, name: str) 
     else:
         policy = fuse_c3_policy()
         allowed = C3_FUSED if policy == "all" else C3_FUSED_AUTO if policy == "auto" else set()
-    if ((src.C, c_, len(m.m), res) in allowed and H % 8 == 0 and W % 16 == 0
+    if (down is None and (src.C, c_, len(m.m), res) in allowed and H % 8 == 0 and W % 16 == 0
             and all(bool(bn.add) == res for bn in m.m)):
         w1, b1 = fold(m.cv1)
         w2, b2 = fold(m.cv2)
@@ -108,11 +118,20 @@ def _c3(pb: ProgramBuilder, m, src: View, dst: View, H: int, W: int, name: str) 
         return
     w1, b1 = fold(m.cv1)
     w2, b2 = fold(m.cv2)
+
+    def first(T):  # cv1 | cv2 into T's first two slots
+        if down is None:
+            pb.conv(src, View(T, 0, 2 * c_), torch.cat([w1, w2]), torch.cat([b1, b2]))
+        else:
+            dsrc, dhw, (wd, bd) = down
+            pb.conv(dsrc, View(BUF_NONE, 0, 2 * c_), wd, bd, stride=2, src_hw=dhw,
+                    pw=(torch.cat([w1, w2]), torch.cat([b1, b2]), View(T, 0, 2 * c_), "silu"))
+
     if pb.f32 and c3_bneck_enabled() and c_ in C3_BNECK_CH:
         # each Bottleneck as one op (csrc/kernels/c3_bneck_x3.hip).  T = [x | y2 | u]: bottleneck i reads slot 0 or
         # 2 and writes the other, so that no launch writes what a neighbouring tile still reads; U disappears
         T = pb.tensor(f"{name}.T", H, W, 3 * c_)
-        pb.conv(src, View(T, 0, 2 * c_), torch.cat([w1, w2]), torch.cat([b1, b2]))
+        first(T)
         cur = 0
         for bn in m.m:
             pb.c3_bneck(View(T, cur * c_, c_), View(T, (2 - cur) * c_, c_), H, W, fold(bn.cv1), fold(bn.cv2),
@@ -126,7 +145,7 @@ def _c3(pb: ProgramBuilder, m, src: View, dst: View, H: int, W: int, name: str) 
         return
     T = pb.tensor(f"{name}.T", H, W, 2 * c_)
     U = pb.tensor(f"{name}.U", H, W, c_)
-    pb.conv(src, View(T, 0, 2 * c_), torch.cat([w1, w2]), torch.cat([b1, b2]))
+    first(T)
     for bn in m.m:
         wa, ba = fold(bn.cv1)
         pb.conv(View(T, 0, c_), View(U, 0, c_), wa, ba)
@@ -209,20 +228,32 @@ def plan_yolo(pb: ProgramBuilder, y: YOLOv5nu, T: int = 640, tensor_input: bool 
     A2 = pb.tensor("b2", h // 2, h // 2, 32)
     _c3(pb, y.b2, View(A1, 0, 32), View(A2, 0, 32), h // 2, h // 2, "b2")
     s8 = T // 8
-    A3 = pb.tensor("b3", s8, s8, 64)
-    pb.conv(View(A2, 0, 32), View(A3, 0, 64), *fold(y.b3), stride=2)
-    CAT16 = pb.tensor("cat16", s8, s8, 128)
-    _c3(pb, y.b4, View(A3, 0, 64), View(CAT16, 64, 64), s8, s8, "b4")
+    if _down_pw(pb, y.b3, y.b4, View(A2, 0, 32)):  # b3 + b4's cv1|cv2 as one kernel: the b3 map is not allocated
+        CAT16 = pb.tensor("cat16", s8, s8, 128)
+        _c3(pb, y.b4, None, View(CAT16, 64, 64), s8, s8, "b4", down=(View(A2, 0, 32), (h // 2, h // 2), fold(y.b3)))
+    else:
+        A3 = pb.tensor("b3", s8, s8, 64)
+        pb.conv(View(A2, 0, 32), View(A3, 0, 64), *fold(y.b3), stride=2)
+        CAT16 = pb.tensor("cat16", s8, s8, 128)
+        _c3(pb, y.b4, View(A3, 0, 64), View(CAT16, 64, 64), s8, s8, "b4")
     s16 = T // 16
-    A5 = pb.tensor("b5", s16, s16, 128)
-    pb.conv(View(CAT16, 64, 64), View(A5, 0, 128), *fold(y.b5), stride=2, src_hw=(s8, s8))
-    CAT12 = pb.tensor("cat12", s16, s16, 256)
-    _c3(pb, y.b6, View(A5, 0, 128), View(CAT12, 128, 128), s16, s16, "b6")
+    if _down_pw(pb, y.b5, y.b6, View(CAT16, 64, 64)):
+        CAT12 = pb.tensor("cat12", s16, s16, 256)
+        _c3(pb, y.b6, None, View(CAT12, 128, 128), s16, s16, "b6", down=(View(CAT16, 64, 64), (s8, s8), fold(y.b5)))
+    else:
+        A5 = pb.tensor("b5", s16, s16, 128)
+        pb.conv(View(CAT16, 64, 64), View(A5, 0, 128), *fold(y.b5), stride=2, src_hw=(s8, s8))
+        CAT12 = pb.tensor("cat12", s16, s16, 256)
+        _c3(pb, y.b6, View(A5, 0, 128), View(CAT12, 128, 128), s16, s16, "b6")
     s32 = T // 32
-    A7 = pb.tensor("b7", s32, s32, 256)
-    pb.conv(View(CAT12, 128, 128), View(A7, 0, 256), *fold(y.b7), stride=2)
-    A8 = pb.tensor("b8", s32, s32, 256)
-    _c3(pb, y.b8, View(A7, 0, 256), View(A8, 0, 256), s32, s32, "b8")
+    if _down_pw(pb, y.b7, y.b8, View(CAT12, 128, 128)):
+        A8 = pb.tensor("b8", s32, s32, 256)
+        _c3(pb, y.b8, None, View(A8, 0, 256), s32, s32, "b8", down=(View(CAT12, 128, 128), (s16, s16), fold(y.b7)))
+    else:
+        A7 = pb.tensor("b7", s32, s32, 256)
+        pb.conv(View(CAT12, 128, 128), View(A7, 0, 256), *fold(y.b7), stride=2)
+        A8 = pb.tensor("b8", s32, s32, 256)
+        _c3(pb, y.b8, View(A7, 0, 256), View(A8, 0, 256), s32, s32, "b8")
     S9 = pb.tensor("sppf", s32, s32, 512)
     c_ = y.b9.c_
     pb.conv(View(A8, 0, 256), View(S9, 0, c_), *fold(y.b9.cv1))

@@ -8,6 +8,7 @@ planner bugs as exceptions on the host instead of GPU faults.
 from __future__ import annotations
 
 from ..engine.planner import (
+    ACT,
     BUF_CTRL,
     BUF_DET,
     BUF_DETCOUNT,
@@ -19,6 +20,7 @@ from ..engine.planner import (
     BUF_XCROPS,
     C3_BNECK_CH,
     CROPS,
+    DOWN_PW_CH,
     OP_AVGPOOL,
     OP_C3BNECK,
     OP_C3FUSED,
@@ -169,8 +171,18 @@ def validate_program(prog: Program, B: int, crop_cap: int, *, max_det: int, cand
             weights(i, int(r[9]), Cpad * 4, "conv bias")
             if int(r[34]) > 0:  # fused pointwise epilogue
                 co2, kpad2, cpad2 = int(r[34]), int(r[32]), int(r[35])
-                if KH != 3 or KW != 3 or int(r[19]) != 1 or Cout not in (64, 80) or kpad2 != (Cout + 31) // 32 * 32 \
-                        or co2 > Cout or int(r[22]) != BUF_NONE or int(r[25]) != BUF_NONE:
+                if int(r[19]) == 2:  # x3ds, csrc/kernels/down_x3.hip (mirror of arena::down_x3_supported)
+                    # the patch reads are those of the 3x3 stride-2 pad-1 conv, inside the input view checked above
+                    if not f32 or (KH, KW, int(r[20]), int(r[21])) != (3, 3, 1, 1) or (Cin, Cout, co2) not in \
+                            DOWN_PW_CH or (Ho, Wo) != ((H - 1) // 2 + 1, (W - 1) // 2 + 1) or kpad2 != Cout or \
+                            Cpad != Cout or int(r[28]) != ACT["silu"] or int(r[39]) != ACT["silu"] or \
+                            int(r[3]) % 4 or int(r[38]) % 4 or int(r[2]) % 4 or int(r[37]) % 4 or \
+                            int(r[22]) != BUF_NONE or int(r[25]) != BUF_NONE or int(r[1]) == int(r[36]) or \
+                            max(n * H * W * int(r[3]), n * Ho * Wo * int(r[38])) * 4 >= 2 ** 31 - 2 ** 20:
+                        raise ProgramError(f"op {i}: unsupported stride-2 fused pointwise geometry")
+                elif KH != 3 or KW != 3 or int(r[19]) != 1 or Cout not in (64, 80) or \
+                        kpad2 != (Cout + 31) // 32 * 32 or co2 > Cout or int(r[22]) != BUF_NONE or \
+                        int(r[25]) != BUF_NONE:
                     raise ProgramError(f"op {i}: unsupported fused pointwise geometry")
                 view(i, r[36], int(r[37]), int(r[38]), n * Ho * Wo, co2, el, "fused pointwise output")
                 # fp32: pre-split planes [round32(co2)][3][kpad2] (pack_pw_weight_x3); bf16: [cpad2][kpad2]

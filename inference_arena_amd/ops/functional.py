@@ -73,7 +73,7 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, stride: in
                 res: torch.Tensor | None = None, res_coff: int = 0, out2: torch.Tensor | None = None,
                 out2_coff: int = 0, f32out: bool = False, out_hw=None, bdev: torch.Tensor | None = None,
                 packed=None, impl: int = 0, pw=None, pw_out: torch.Tensor | None = None, pw_out_coff: int = 0,
-                gate=None, window=None, marks=None, x_planes: bool = False,
+                pw_act: str | None = None, gate=None, window=None, marks=None, x_planes: bool = False,
                 out_planes: torch.Tensor | None = None, planes_only: bool = False) -> torch.Tensor:
     """NHWC conv with fused bias/act/residual/upsampled copy.
 
@@ -88,7 +88,14 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, stride: in
     [B, ceil(Ho / 8), ceil(Wo / 8)] cell marks (``head_mark``); an output tile that no continuing ``uh`` x ``uw``
     consumer tile grown by ``halo`` pixels reads is skipped and keeps its contents (ConvParams.marks).
 
-    ``pw=(w2, b2)`` (fp32 3x3 stride-1 only): the Detect-head 1x1 ``w2`` [C2, Cout, 1, 1] is applied to the
+    ``pw=(w2, b2)`` with ``stride=2`` (fp32 only; x3ds, csrc/kernels/down_x3.hip): a backbone downsampling pair as one
+    kernel, ``silu(w2 . silu(conv3x3_s2_pad1(x, w) + b) + b2)`` with ``act="silu"``, ``pw_act="silu"``, (Cin, Cout) =
+    (32, 64), (64, 128) or (128, 256) and C2 == Cout; ``impl`` 145 + v names tile v (0: 4 x 16, 1: 4 x 20, 2: 2 x 20
+    output pixels), any other ``impl`` lets the launcher choose.  ``gate``, ``window``, ``marks`` and planes are not
+    options of it, and the output must not overlap the input.  ``pw_act`` is the activation after the 1x1 (None for
+    the Detect-head epilogues below).
+
+    ``pw=(w2, b2)`` (otherwise: fp32 3x3 stride-1 only): the Detect-head 1x1 ``w2`` [C2, Cout, 1, 1] is applied to the
     activated result inside the x3hg epilogue (impl 145 + v) and only its [B, Ho, Wo, C2] output is returned (a
     bf16 ``x``: the v3 halo-tile kernel's epilogue, csrc/kernels/conv3x3_v3.hip, bf16 output);
     ``pw_out`` (float32 / bf16 as the output, [B, Ho, Wo, C], optional): write those C2 channels at ``pw_out_coff`` of it instead and
@@ -111,6 +118,17 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, stride: in
         raise ValueError("conv2d_nhwc: window, gate and marks are not x3hc options (the family runs the whole "
                          "80-channel conv on every tile)")
     cout, cin_w, kh, kw = w.shape
+    if pw is not None and stride == 2:
+        if x.dtype != torch.float32 or x_planes:
+            raise ValueError("conv2d_nhwc: the stride-2 fused 1x1 (x3ds) is an fp32 kernel over an fp32 input")
+        if not (gate is None and window is None and marks is None and out_planes is None and res is None
+                and out2 is None):
+            raise ValueError("conv2d_nhwc: gate, window, marks, planes, res and out2 are not options of the stride-2 "
+                             "fused 1x1 (x3ds)")
+        if ((cin or cin_w, cout) not in ((32, 64), (64, 128), (128, 256)) or (kh, kw) != (3, 3)
+                or tuple(pw[0].shape) != (cout, cout, 1, 1) or act != "silu" or pw_act != "silu"):
+            raise ValueError("conv2d_nhwc: the stride-2 fused 1x1 (x3ds) takes a 3x3 conv with (Cin, Cout) = (32, 64), "
+                             "(64, 128) or (128, 256), a 1x1 Cout -> Cout and SiLU after both")
     if x_planes:
         if x_coff or (cin is not None and cin != cin_w) or cin_w % 32:
             raise ValueError("conv2d_nhwc: a planes input is one whole activation (x_coff 0, Cin % 32 == 0)")
@@ -168,7 +186,12 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, stride: in
                     or out.device != x.device or not out.is_contiguous()):
                 raise ValueError(f"conv2d_nhwc: pw_out {tuple(out.shape)} {out.dtype} does not fit the 1x1 output")
         pwd = {"pw_w": _ptr(w2p), "pw_bias": _ptr(b2p), "pw_y": _ptr(out, pw_out_coff), "pw_ys": out.shape[-1],
-               "pw_cout": co2, "pw_kpad": k2, "pw_act": 0}
+               "pw_cout": co2, "pw_kpad": k2, "pw_act": ACT[pw_act]}
+        if stride == 2:  # every workgroup reads its neighbours' input pixels
+            x_lo, x_hi = x.data_ptr(), x.data_ptr() + x.numel() * 4
+            o_lo, o_hi = out.data_ptr(), out.data_ptr() + out.numel() * 4
+            if x_lo < o_hi and o_lo < x_hi:
+                raise ValueError("conv2d_nhwc: the stride-2 fused 1x1 (x3ds) output must not overlap the input")
         if gate is not None:
             gt, gcoff, gn, gmin = gate
             if (gt.shape != out.shape or gt.dtype != torch.float32 or gt.device != x.device or not gt.is_contiguous()

@@ -53,6 +53,7 @@ SOURCES = [
     "kernels/c3_fused.hip",
     "kernels/c3_x3.hip",
     "kernels/c3_bneck_x3.hip",
+    "kernels/down_x3.hip",
     "kernels/preprocess.hip",
     "kernels/stem_fused.hip",
     "kernels/detect.hip",
@@ -90,7 +91,10 @@ SOURCES = [
 # gemm_x3p.hip, new as well, likewise: its planes store splits with the two-at-a-time form.
 # c3_bneck_x3.hip, new as well, likewise (both of its splits use the two-at-a-time form): 106 / 118 / 122 VGPRs + 24 / 44 /
 # 76 AGPRs and no scratch for c_ = 32 / 64 / 128, so register pressure asks for nothing either way.
+# down_x3.hip, new as well, likewise (both of its splits use the two-at-a-time form): no scratch in any of its nine
+# instantiations, at most 248 VGPRs + 108 AGPRs (Cin 128 -> C 256 on the 4 x 20 tile).
 PER_FILE_FLAGS: dict[str, list[str]] = {
+    "down_x3.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "c3_bneck_x3.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "gemm_x3p.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "halo_x3c.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
