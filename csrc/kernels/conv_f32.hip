@@ -1565,13 +1565,17 @@ void conv2d_f32(const ConvParams& p, hipStream_t s) {
     conv_down_x3(p, s);
     return;
   }
-  if (p.pw_w != nullptr) {  // fused Detect-head 1x1: the x3hg / x3hr epilogue variants and x3hc implement it
+  if (p.pw_w != nullptr) {  // fused Detect-head 1x1: the x3hg / x3hr epilogue variants, x3hc and split-K x3g implement it
     if (f32_conv_impl_in(p.impl, F32Family::X3HC)) {
       if (!conv_x3hc(p, s, p.impl - kF32X3HC)) throw std::runtime_error(f32_family(F32Family::X3HC).reject);
       return;
     }
     if (f32_conv_impl_in(p.impl, F32Family::X3HRPw)) {
       if (!conv_x3hr_pw(p, s, p.impl - kF32X3HRPw)) throw std::runtime_error(f32_family(F32Family::X3HRPw).reject);
+      return;
+    }
+    if (f32_conv_impl_in(p.impl, F32Family::X3GSK)) {  // split-K 3x3, the 1x1 in the reduce pass (sk_pw_x3.hip)
+      conv_x3g_sk_pw(p, s, p.impl - kF32X3GSK);
       return;
     }
     const int v = x3hg_pw_variant(p.impl, p.Cout_pad);

@@ -311,6 +311,7 @@ void prepare_kernels() {
   head_pool_f32_prepare();
   x3_halo_prepare();
   x3g_prepare();
+  x3g_sk_pw_prepare();
   x3gp_prepare();
   c3_x3_prepare();
   c3_bneck_x3_prepare();

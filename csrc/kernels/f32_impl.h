@@ -59,7 +59,8 @@ constexpr uint32_t f32_all(int n) { return (1u << n) - 1u; }
   /* x3hp: the 16x16x32 halo tiles of X3Halo* over the pre-split weights (halo_x3p.hip HP_VARIANTS), bit-identical   \
      to impl 101 / 102 / 103 / 108 / 109 on every conv they take; variant 9 serves the head split only */             \
   X(X3HP, 191, 10, f32_all(9), "conv2d_f32: not an x3hp-eligible conv (3x3 s1 with pre-split weights)")               \
-  /* split-K x3g for small grids (XG_SK_VARIANTS: tile x splits); needs ConvParams.sk_ws */                           \
+  /* split-K x3g for small grids (XG_SK_VARIANTS: tile x splits); needs ConvParams.sk_ws.  On a 3x3 stride-1 record   \
+     with a fused 1x1 (pw_*): the same first pass, the 1x1 applied to the reduced tile (sk_pw_x3.hip) */              \
   X(X3GSK, 171, 9, f32_all(9), "conv2d_f32: not a split-K x3g-eligible conv (pre-split weights, workspace)")           \
   /* x3hc: exact 80-channel 16-wide halo tiles for the Detect head's class branch, with or without the fused 1x1    \
      (halo_x3c.hip HC_VARIANTS) */                                                                                    \

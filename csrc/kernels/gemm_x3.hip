@@ -45,7 +45,9 @@ __host__ __device__ constexpr int xg_lds_bytes(int BM, int BN) { return 2 * (BM 
 // IL: shape the schedule of each K step (sched_group_barrier) so the next chunk's split arithmetic and LDS stores
 // issue between this chunk's MFMAs instead of after them (a wave's vector issue is free for 24 of each
 // 32x32x16 MFMA's 32 cycles)
-template <int WM, int WN, int TM, int TN, bool IL = false, bool SK = false>
+// GATE (split-K pass 1 of a fused-1x1 record, sk_pw_x3.hip): honour the tile gate (ConvParams.gate) on the BM-pixel
+// linear tile; every other instantiation keeps its instruction stream
+template <int WM, int WN, int TM, int TN, bool IL = false, bool SK = false, bool GATE = false>
 __global__ __launch_bounds__(WM * WN * 64) void conv_x3g_kernel(const ConvParams p) {
   constexpr int NT = WM * WN * 64;  // 4 or 8 waves
   static_assert(WM * WN == 4 || WM * WN == 8, "four or eight waves");
@@ -71,6 +73,23 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_x3g_kernel(const ConvParams
   const int mt = bx / ntn, nt = bx - mt * ntn;
   const int m0 = mt * BM, n0 = nt * BN;
   if (m0 >= M) return;
+
+  // ---- tile gate: nothing reads this tile's partial sums unless one of its pixels holds a gating logit >= gate_min
+  // (the second pass applies the same rule to pixel tiles that divide this one); before any operand load
+  if constexpr (GATE) {
+    if (p.gate != nullptr) {
+      const int nq = p.gate_n >> 2;  // host: gate_n % 4 == 0
+      const int items = (M - m0 < BM ? M - m0 : BM) * nq;
+      const float gm = p.gate_min;
+      int any = 0;
+      for (int i = tid; i < items; i += NT) {
+        const int px = i / nq, q = i - px * nq;
+        const float4 g = *(const float4*)(p.gate + (size_t)(m0 + px) * p.pw_ys + 4 * q);
+        any |= g.x >= gm || g.y >= gm || g.z >= gm || g.w >= gm;  // NaN compares false
+      }
+      if (!__syncthreads_or(any)) return;
+    }
+  }
 
   // Operands are read with raw buffer loads: an out-of-range offset (conv padding, pixels past the live batch,
   // channels past Cin) returns zeros without a select per dword, offsets are 32-bit, and the weight offsets
@@ -360,22 +379,25 @@ void xg_launch(const ConvParams& p, hipStream_t s) {
 }
 
 // split-K: tile variant (XG_VARIANTS id) x splits; a workspace of splits x B x Ho x Wo x Cout_pad fp32 (ConvParams
-// sk_ws, per executor slot) holds the partial tiles
-template <int WM, int WN, int TM, int TN>
-bool xg_launch_sk(const ConvParams& p, hipStream_t s, int splits) {
+// sk_ws, per executor slot) holds the partial tiles.  Returns the splits launched (at most one K chunk each), 0 with
+// nothing launched where the workspace cannot hold them or a single split is left.
+// PW: the first pass alone, gated, for the fused-1x1 second pass of sk_pw_x3.hip, whose 64- / 32-pixel tiles divide BM
+template <int WM, int WN, int TM, int TN, bool PW = false>
+int xg_launch_sk(const ConvParams& p, hipStream_t s, int splits) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
+  static_assert(BM % 64 == 0, "second-pass tiles of 64 / 32 pixels divide a first-pass tile");
   const long M = (long)p.B * p.Ho * p.Wo;
   const int nk = p.KH * p.KW * ((p.Cin + 31) / 32);
-  splits = splits < nk ? splits : nk;  // at most one K chunk per split
+  splits = splits < nk ? splits : nk;
   if (p.sk_ws == nullptr || splits < 2 || (long)splits * M * p.Cout_pad * 4 > p.sk_ws_bytes || p.Cout_pad % 4)
-    return false;
+    return 0;
   const long tiles = ((M + BM - 1) / BM) * ((p.Cout_pad + BN - 1) / BN);
   ConvParams q = p;
   q.sk_splits = splits;
-  hipLaunchKernelGGL((conv_x3g_kernel<WM, WN, TM, TN, false, true>), dim3((unsigned)(tiles * splits)),
+  hipLaunchKernelGGL((conv_x3g_kernel<WM, WN, TM, TN, false, true, PW>), dim3((unsigned)(tiles * splits)),
                      dim3(WM * WN * 64), xg_lds_bytes(BM, BN), s, q);
-  x3g_sk_reduce(q, s);
-  return true;
+  if (!PW) x3g_sk_reduce(q, s);
+  return splits;
 }
 
 #define XG_SK_VARIANTS(X) \
@@ -444,6 +466,19 @@ bool conv_x3g_sk(const ConvParams& p, hipStream_t s, int v) {
   }
 }
 
+int x3g_sk_pass1(const ConvParams& p, hipStream_t s, int v) {
+  ConvParams q = p;  // the 3x3 conv alone
+  q.pw_w = nullptr;
+  if (!x3g_supported(q)) return 0;
+  switch (v) {
+#define XG_SK_P1(V, WM, WN, TM, TN, S) \
+  case V: return xg_launch_sk<WM, WN, TM, TN, true>(p, s, S);
+    XG_SK_VARIANTS(XG_SK_P1)
+#undef XG_SK_P1
+    default: return 0;
+  }
+}
+
 void x3g_prepare() {
 #define XG_ATTR(V, WM, WN, TM, TN)                                                                       \
   ARENA_HIP_CHECK(hipFuncSetAttribute((const void*)conv_x3g_kernel<WM, WN, TM, TN, false>,                \
@@ -456,6 +491,9 @@ void x3g_prepare() {
 #undef XG_ATTR
 #define XG_SK_ATTR(V, WM, WN, TM, TN, S)                                                                  \
   ARENA_HIP_CHECK(hipFuncSetAttribute((const void*)conv_x3g_kernel<WM, WN, TM, TN, false, true>,          \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize,                         \
+                                      xg_lds_bytes(WM * TM * 32, WN * TN * 32)));                         \
+  ARENA_HIP_CHECK(hipFuncSetAttribute((const void*)conv_x3g_kernel<WM, WN, TM, TN, false, true, true>,    \
                                       hipFuncAttributeMaxDynamicSharedMemorySize,                         \
                                       xg_lds_bytes(WM * TM * 32, WN * TN * 32)));
   XG_SK_VARIANTS(XG_SK_ATTR)

@@ -50,7 +50,8 @@ struct ConvParams {
   const float* pw_bias; // fp32 [pw_cout_pad]
   void* pw_y;           // bf16 output, pixel stride pw_ys
   int pw_ys, pw_cout, pw_kpad, pw_act;
-  // Optional tile gate (x3hg fused-1x1 kernels only, every other conv kernel ignores it; nullptr = off): fp32
+  // Optional tile gate (x3hg fused-1x1 kernels and both passes of split-K x3g on such a record, sk_pw_x3.hip, over
+  // linear pixel tiles; every other conv kernel ignores it; nullptr = off): fp32
   // logits with the pixel indexing and pixel stride of pw_y.  A workgroup whose in-map tile pixels hold no
   // logit >= gate_min among their first gate_n channels (a multiple of 4, 16-byte aligned) returns before it
   // loads anything else and writes nothing (NaN compares false); a tile that continues is computed as without
@@ -111,6 +112,15 @@ void x3g_prepare();
 // the split-K second pass of conv_x3g_sk on its own: y = act(sum over sk_splits partial tiles in sk_ws + bias) (+ res)
 // from B, Ho, Wo, Cout, Cout_pad, bias, act, res / rs, y / ys, y2 / y2s, bdev, sk_ws, sk_splits
 void x3g_sk_reduce(const ConvParams& p, hipStream_t s);
+// the split-K first pass of XG_SK_VARIANTS row v alone, on a record whose pw_w is set: raw partial tiles of the 3x3 conv
+// into sk_ws, tiles without a passing gate logit (ConvParams.gate) skipped.  Returns the splits written, 0 with nothing
+// launched where the conv is not x3g's, the workspace cannot hold the partials or a single split is left.
+int x3g_sk_pass1(const ConvParams& p, hipStream_t s, int v);
+// split-K x3g with the fused Detect-head 1x1 in the reduce pass (sk_pw_x3.hip): impl kF32X3GSK + v on a record whose
+// pw_w is set.  Throws std::runtime_error naming what it does not take; where the workspace cannot hold the partials
+// it runs the default fused x3hg variant instead.
+void conv_x3g_sk_pw(const ConvParams& p, hipStream_t s, int v);
+void x3g_sk_pw_prepare();
 // x3gp (gemm_x3p.hip): tile v (XG_VARIANTS 0..9; v + 10 is the same tile) of the x3g GEMM reading and / or writing
 // x3 planes (ConvParams.x_planes, y3); throws std::runtime_error naming what it does not take
 void conv_x3gp(const ConvParams& p, hipStream_t s, int v);

@@ -579,8 +579,8 @@ uint8_t* Executor::resolve(Bucket& bk, Slot& sl, int64_t buf, int64_t coff, int 
 // independent, so the buffers of both are live across both positions in either order.  A pair stays in program
 // order and ungated when its two ops are not both in this enqueue segment (a stagger split point between them,
 // a single op of the debug modes), when an op is being timed (force_impl: timings stay dense-cost, and
-// the logits buffer holds nothing meaningful then) and when the kernel chosen for the box conv is not an x3hg
-// fused-1x1 variant.  The gate is advisory: an ungated op is merely slower, never wrong.
+// the logits buffer holds nothing meaningful then) and when the kernel chosen for the box conv is neither an x3hg
+// fused-1x1 variant nor a split-K x3g impl (sk_pw_x3.hip).  The gate is advisory: an ungated op is merely slower, never wrong.
 std::vector<size_t> Executor::exec_plan(const std::vector<OpRecord>& prog, const Bucket& bk, int op_offset,
                                         int force_impl, std::vector<const HeadGatePair*>& gate) const {
   std::vector<size_t> order(prog.size());
@@ -595,7 +595,8 @@ std::vector<size_t> Executor::exec_plan(const std::vector<OpRecord>& prog, const
     if (prog[li] != prog_[gp.box] || prog[li + 1] != prog_[gp.cls]) continue;  // not that slice of prog_
     const int impl = gp.box < (int)bk.impl.size() ? bk.impl[gp.box] : 0;
     const bool x3hg_pw = impl == 0 || f32_conv_impl_in(impl, F32Family::X3HGPw) ||
-                         f32_conv_impl_in(impl, F32Family::X3HGPwSmall);
+                         f32_conv_impl_in(impl, F32Family::X3HGPwSmall) ||
+                         f32_conv_impl_in(impl, F32Family::X3GSK);  // both split-K passes honour the gate
     if (!x3hg_pw) continue;
     order[li] = (size_t)li + 1;
     order[li + 1] = (size_t)li;

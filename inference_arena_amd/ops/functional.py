@@ -96,7 +96,8 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, stride: in
     the Detect-head epilogues below).
 
     ``pw=(w2, b2)`` (otherwise: fp32 3x3 stride-1 only): the Detect-head 1x1 ``w2`` [C2, Cout, 1, 1] is applied to the
-    activated result inside the x3hg epilogue (impl 145 + v) and only its [B, Ho, Wo, C2] output is returned (a
+    activated result inside the x3hg epilogue (impl 145 + v), or, with a split-K x3g impl 171 + v, to the reduced tile
+    in the second pass (csrc/kernels/sk_pw_x3.hip; the gate applies), and only its [B, Ho, Wo, C2] output is returned (a
     bf16 ``x``: the v3 halo-tile kernel's epilogue, csrc/kernels/conv3x3_v3.hip, bf16 output);
     ``pw_out`` (float32 / bf16 as the output, [B, Ho, Wo, C], optional): write those C2 channels at ``pw_out_coff`` of it instead and
     return it.  ``gate=(logits, coff, n, gate_min)`` (x3hg fused-1x1 kernels only): float32 ``logits`` with the shape

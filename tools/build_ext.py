@@ -33,6 +33,7 @@ SOURCES = [
     "kernels/conv_f32.hip",
     "kernels/gemm_x3.hip",
     "kernels/gemm_x3p.hip",
+    "kernels/sk_pw_x3.hip",
     "kernels/halo_x3g.hip",
     "kernels/halo_x3p.hip",
     "kernels/halo_x3c.hip",
@@ -93,7 +94,9 @@ SOURCES = [
 # 76 AGPRs and no scratch for c_ = 32 / 64 / 128, so register pressure asks for nothing either way.
 # down_x3.hip, new as well, likewise (both of its splits use the two-at-a-time form): no scratch in any of its nine
 # instantiations, at most 248 VGPRs + 108 AGPRs (Cin 128 -> C 256 on the 4 x 20 tile).
+# sk_pw_x3.hip, new as well, likewise (its one split uses the two-at-a-time form); no scratch in its six instantiations.
 PER_FILE_FLAGS: dict[str, list[str]] = {
+    "sk_pw_x3.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "down_x3.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "c3_bneck_x3.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "gemm_x3p.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
